@@ -12,9 +12,17 @@ arithmetic type of the hash/scatter path, not a precision claim. Inputs are resi
 HBM when the timed region starts; the PCIe-inclusive staging rate is reported in
 config.h2d_GBps (never as value).
 
-cpu_baseline: the C oracle (oracle/dd_oracle.c — same algorithm; kind "port"; the
-reference itself is Rust and unbuildable here) timed on this box's host
-cores on a bounded sample. Rank 0, N=1 only.
+A plain run (--gpus/--steps/--warmup) only sets up, warms up, times the steps and prints
+the result line. --full adds the legs that take runs of their own: the cpu_baseline and,
+at N>1, the extra exchange behind config.xgmi_egress_GBps (both null/absent otherwise).
+
+cpu_baseline (--full): the C oracle (oracle/dd_oracle.c — same algorithm; kind "port";
+the reference itself is Rust and unbuildable here) timed on the host cores
+on a bounded sample. Rank 0, N=1 only.
+
+--dump-outputs DIR writes what the last timed step computed (partition row offsets and
+the partition-major output columns, cut to a fixed seeded row sample when large) as
+DIR/<name>.npy, so two builds can be compared output for output on the same inputs.
 
 --workload selects additional BASELINE config shapes for extra evidence lines
 (tpch_sf1_q1_repartition = config[1]; clickbench_userid_shuffle = config[4] stand-in);
@@ -205,6 +213,55 @@ def cpu_baseline_leg(rows_sample, key, cols_np, min_seconds=8.0, max_seconds=30.
     }
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # split over the ranks; the whole dump stays under 64 MB
+DUMP_SEED = 20240229
+# exact in the dumped type: f64/i64/i32 go to float64, the narrow types to float32
+DUMP_NP = {"f64": np.float64, "i64": np.float64, "i32": np.float64, "dict32": np.float64,
+           "f32": np.float32, "i16": np.float32, "u8": np.float32, "bool": np.float32}
+
+
+def dump_outputs(part, out_dir, prefix="", budget=DUMP_BUDGET_BYTES):
+    """Write what the last run of `part` left for its caller — row_offsets and every
+    partition-major output column — as float32/float64 .npy files under out_dir. Outputs
+    over the byte budget are cut to a seeded sample of output rows (the same rows on every
+    run; the scatter is stable, so equal builds give equal files)."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), arr)
+
+    cols = part.batch.cols
+    n = part.batch.n_rows
+    save("row_offsets", part.row_offsets().astype(np.float64))
+    per_row = 8  # the sampled row index itself
+    for c in cols:
+        # utf8: a float64 length per sampled row + as many float32 byte samples
+        per_row += 12 if c["dtype"] == "utf8" else np.dtype(DUMP_NP[c["dtype"]]).itemsize
+        per_row += 4 if c.get("valid") is not None else 0
+    k = budget // per_row
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = None if n <= k else np.sort(rng.integers(0, n, k))
+    if rows is not None:
+        save("sample_rows", rows.astype(np.float64))
+    for i, c in enumerate(cols):
+        out = part.col_out(i)
+        name = f"col{i}_{c['dtype']}"
+        if c["dtype"] == "utf8":
+            nb = len(out["data"])
+            at = None if nb <= k else np.sort(rng.integers(0, nb, k))
+            save(name + "_bytes", (out["data"] if at is None else out["data"][at])
+                 .astype(np.float32))
+            lens = out["lengths"]
+            save(name + "_lengths", (lens if rows is None else lens[rows])
+                 .astype(np.float64))
+        else:
+            d = out["data"]
+            save(name, (d if rows is None else d[rows]).astype(DUMP_NP[c["dtype"]]))
+        if "valid" in out:
+            v = out["valid"]
+            save(name + "_valid", (v if rows is None else v[rows]).astype(np.float32))
+
+
 def run_ingest(args):
     """Pinned-host staged ingest (VERDICT r01 item 8 / DESIGN §11.4): the real pipeline's
     input arrives from host-side parquet scans. Double-buffered PINNED staging chunks are
@@ -281,6 +338,8 @@ def run_ingest(args):
     dt = time.perf_counter() - t0
     total = nbytes * nchunks
     kms = parts[0].kernel_ms()
+    if args.dump_outputs:
+        dump_outputs(parts[(nchunks - 1) % 2], args.dump_outputs)
     line = {
         "metric": "tpch_sf10_staged_ingest_GBps",
         "value": round(total / dt / 1e9, 2),
@@ -319,7 +378,16 @@ def main():
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="measured HBM bytes per K3 launch from a separate rocprofv3 "
                          "--pmc run (profiles/); null if not provided")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the cpu_baseline "
+                         "(C oracle on the host cores, N=1) and, at N>1, the extra "
+                         "exchange behind config.xgmi_egress_GBps")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the cpu_baseline leg out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed "
+                         "(row offsets + partition-major output columns, seeded row "
+                         "sample when large) as DIR/<name>.npy in float32/float64")
     ap.add_argument("--ingest", action="store_true",
                     help="pinned-host staged-ingest pipeline: double-buffered H2D on a "
                          "copy stream overlapped with the partition kernels (the "
@@ -341,7 +409,11 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", str(args.gpus)))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 
-    import torch
+    # the plain N=1 run drives the C ABI alone; torch (seconds to import) is loaded only
+    # for the process group at N>1 and the streams of --pipeline
+    torch = None
+    if world > 1 or args.pipeline:
+        import torch
 
     if world > 1:
         import torch.distributed as dist
@@ -353,7 +425,7 @@ def main():
         backend = "nccl" if ndev >= world else "gloo"
         dist.init_process_group(backend, rank=rank, world_size=world)
         torch.cuda.set_device(local_rank % max(ndev, 1))
-    elif torch.cuda.is_available():
+    elif torch is not None and torch.cuda.is_available():
         torch.cuda.set_device(0)
 
     from datafusion_distributed_amd import api
@@ -384,7 +456,8 @@ def main():
         # u8 pid array (pre path, P <= 256): K3 reads 1 B/row of pid, not 4
         k3_bytes -= 3 * rows
     comm = create_comm(rank, world) if world > 1 else None
-    pipeline = world == 1 and args.pipeline and torch.cuda.is_available()
+    have_torch_gpu = torch is not None and torch.cuda.is_available()
+    pipeline = world == 1 and args.pipeline and have_torch_gpu
     if pipeline:
         part2 = api.Partitioner(batch, key_idx, p_total)
         parts2 = [part, part2]
@@ -420,7 +493,7 @@ def main():
 
             torch.cuda.synchronize()
             dist.barrier()
-        torch.cuda.synchronize() if torch.cuda.is_available() else api.lib().dd_device_sync()
+        torch.cuda.synchronize() if have_torch_gpu else api.lib().dd_device_sync()
 
     for _ in range(args.warmup):
         if pipeline:
@@ -465,8 +538,13 @@ def main():
         "traffic": args.traffic_bytes,
     }
 
+    if args.dump_outputs:
+        last = parts2[(args.steps - 1) % 2] if pipeline else part
+        dump_outputs(last, args.dump_outputs, f"rank{rank}_" if world > 1 else "",
+                     DUMP_BUDGET_BYTES // world)
+
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.skip_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.skip_cpu_baseline:
         cpu_baseline = cpu_baseline_leg(min(rows, 8_000_000), key_idx, cols_np)
 
     config = {
@@ -483,10 +561,11 @@ def main():
         "h2d_GBps": round(h2d_gbps, 2),
     }
     if comm is not None:
+        config["data_plane"] = getattr(comm, "data_plane", "rccl/xgmi")
+    if comm is not None and args.full:
         ex = comm.exchange(part)
         ms, egress = ex.stats()
         config["xgmi_egress_GBps"] = round(egress / (ms / 1e3) / 1e9, 2) if ms > 0 else None
-        config["data_plane"] = getattr(comm, "data_plane", "rccl/xgmi")
         ex.destroy()
 
     line = {
