@@ -97,6 +97,13 @@ def lib():
         L.dd_bcast_col_offsets.restype = ctypes.c_void_p
         L.dd_reducer_n_rows.restype = ctypes.c_int64
         L.dd_reducer_kernel_ms.restype = ctypes.c_float
+        L.dd_dict_gc_n_windows.restype = ctypes.c_uint32
+        L.dd_dict_gc_indices.restype = ctypes.c_void_p
+        L.dd_dict_gc_dict_offsets.restype = ctypes.c_void_p
+        L.dd_dict_gc_dict_bytes.restype = ctypes.c_void_p
+        L.dd_exchanged_dict_n.restype = ctypes.c_int64
+        L.dd_exchanged_dict_offsets.restype = ctypes.c_void_p
+        L.dd_exchanged_dict_bytes.restype = ctypes.c_void_p
         _lib = L
     return _lib
 
@@ -310,6 +317,57 @@ class Partitioner:
             self.h = None
 
 
+class DictGC:
+    """Per-window dictionary GC of one dict32 column of a run Partitioner (dd_dict_gc_*,
+    DESIGN.md §14): window-local indices plus one compacted dictionary per window. The
+    partitioner's own output is untouched and must outlive this object."""
+
+    def __init__(self, part: Partitioner, col: int, n_windows: int, stream=None):
+        self.part = part
+        self.col = col
+        self.n_windows = n_windows
+        self.h = ctypes.c_void_p()
+        _check(lib().dd_dict_gc_run(part.h, col, ctypes.c_uint32(n_windows),
+                                    _stream_arg(stream), ctypes.byref(self.h)))
+        self._counts = None
+
+    def counts(self):
+        """(val_off, byte_off): host prefix sums i64[n_windows+1] of values / bytes."""
+        if self._counts is None:
+            v = np.empty(self.n_windows + 1, dtype=np.int64)
+            b = np.empty(self.n_windows + 1, dtype=np.int64)
+            _check(lib().dd_dict_gc_counts(
+                self.h, v.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                b.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            self._counts = (v, b)
+        return self._counts
+
+    def indices(self):
+        """Download the remapped i32[n_rows] indices (0 for null rows)."""
+        return _d2h(lib().dd_dict_gc_indices(self.h), self.part.batch.n_rows * 4, np.int32)
+
+    def window_dict(self, w):
+        """Download window w's compacted dictionary: (offsets i32[nvals+1], bytes u8)."""
+        v, b = self.counts()
+        nv, nb = int(v[w + 1] - v[w]), int(b[w + 1] - b[w])
+        off = _d2h(lib().dd_dict_gc_dict_offsets(self.h) + (int(v[w]) + w) * 4,
+                   (nv + 1) * 4, np.int32)
+        data = (_d2h(lib().dd_dict_gc_dict_bytes(self.h) + int(b[w]), nb, np.uint8)
+                if nb else np.zeros(0, dtype=np.uint8))
+        return off, data
+
+    def kernel_ms(self):
+        """[mark, rank, compact, remap] hipEvent durations of the run, in ms."""
+        out = (ctypes.c_float * 4)()
+        _check(lib().dd_dict_gc_kernel_ms(self.h, out))
+        return list(out)
+
+    def destroy(self):
+        if self.h:
+            lib().dd_dict_gc_destroy(self.h)
+            self.h = None
+
+
 class Comm:
     """RCCL communicator (dd_comm_*)."""
 
@@ -326,10 +384,17 @@ class Comm:
         _check(lib().dd_comm_unique_id(buf))
         return buf.raw
 
-    def exchange(self, part: Partitioner, stream=None):
+    def exchange(self, part: Partitioner, stream=None, gc=None):
+        """gc: a list of DictGC (n_windows == nranks) routes to dd_exchange_run_gc — those
+        columns cross with their compacted dictionaries (Exchanged.col_dict)."""
         h = ctypes.c_void_p()
-        _check(lib().dd_exchange_run(self.h, part.h, _stream_arg(stream),
-                                     ctypes.byref(h)))
+        if gc is None:
+            _check(lib().dd_exchange_run(self.h, part.h, _stream_arg(stream),
+                                         ctypes.byref(h)))
+        else:
+            gcs = (ctypes.c_void_p * max(len(gc), 1))(*[g.h.value for g in gc])
+            _check(lib().dd_exchange_run_gc(self.h, part.h, gcs, len(gc),
+                                            _stream_arg(stream), ctypes.byref(h)))
         return Exchanged(h, part, self)
 
     def coalesce(self, part: Partitioner, consumer_tasks: int, stream=None):
@@ -438,6 +503,19 @@ class Exchanged:
     def col_validity(self, i):
         vp = lib().dd_exchanged_col_validity(self.h, i)
         return _d2h(vp, self.total_rows, np.uint8) if vp else None
+
+    def col_dict(self, i):
+        """Received dictionary of a GC'd dict32 column (its col_data holds the rebased
+        indices): {"offsets": i32[dict_n+1], "bytes": u8, "vals_per_producer": i64}."""
+        vpp = np.empty(self.comm.nranks, dtype=np.int64)
+        _check(lib().dd_exchanged_dict_counts(
+            self.h, i, vpp.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        dn = int(lib().dd_exchanged_dict_n(self.h, i))
+        off = _d2h(lib().dd_exchanged_dict_offsets(self.h, i), (dn + 1) * 4, np.int32)
+        nb = int(off[-1])
+        data = (_d2h(lib().dd_exchanged_dict_bytes(self.h, i), nb, np.uint8)
+                if nb else np.zeros(0, dtype=np.uint8))
+        return {"offsets": off, "bytes": data, "vals_per_producer": vpp}
 
     def stats(self):
         ms = ctypes.c_float()

@@ -28,10 +28,32 @@ def _validity_mask(valid_u8):
     return valid_u8.astype(bool) if valid_u8 is not None else None
 
 
-def partition_batches(part, lo, hi, batch_size=8192):
+def _utf8_values(pa, offsets, data):
+    # Rebuild values from the raw offsets/bytes buffers: the device path hashes/moves raw
+    # bytes, so round-tripping through str would silently mutate (or mask) non-UTF8
+    # dictionary bytes.
+    doff = np.asarray(offsets, dtype=np.int32)
+    dbuf = np.asarray(data, dtype=np.uint8)
+    return pa.StringArray.from_buffers(
+        len(doff) - 1, pa.py_buffer(doff.tobytes()), pa.py_buffer(dbuf.tobytes()), None)
+
+
+def partition_batches(part, lo, hi, batch_size=8192, gc=None):
     """Arrow RecordBatches for partitions [lo, hi) of a run Partitioner (downloads the
-    partition-major buffers once and slices views). Yields (partition, RecordBatch)."""
+    partition-major buffers once and slices views). Yields (partition, RecordBatch).
+
+    gc: optional {col: DictGC} run with n_windows == part.nparts (one dictionary per
+    partition, the reference's per-batch granularity, worker_service.rs:363-433): those
+    columns' DictionaryArrays use the remapped indices and the partition's compacted
+    dictionary. Without it every batch carries the full input dictionary."""
     pa = _arrow()
+    gc = gc or {}
+    gc_idx = {}
+    for i, g in gc.items():
+        if g.n_windows != part.nparts or g.part is not part:
+            raise ValueError("partition_batches: DictGC must be run on this partitioner "
+                             "with n_windows == part.nparts")
+        gc_idx[i] = g.indices()
     roff = part.row_offsets()
     cols_meta = part.batch.cols
     fixed = {}
@@ -52,6 +74,7 @@ def partition_batches(part, lo, hi, batch_size=8192):
 
     for p in range(lo, hi):
         r0, r1 = int(roff[p]), int(roff[p + 1])
+        pdict = {}  # this partition's compacted dictionaries (gc columns)
         # one empty batch for an empty partition (the reference emits empty streams)
         slices = [(r0, r0)] if r1 == r0 else [
             (b0, min(b0 + batch_size, r1)) for b0 in range(r0, r1, batch_size)]
@@ -76,19 +99,14 @@ def partition_batches(part, lo, hi, batch_size=8192):
                         pa.py_buffer(np.packbits(~mask, bitorder="little").tobytes())
                         if mask is not None else None,
                     )
+                elif c["dtype"] == "dict32" and i in gc:
+                    idx = pa.array(gc_idx[i][b0:b1], type=pa.int32(), mask=mask)
+                    if i not in pdict:
+                        pdict[i] = _utf8_values(pa, *gc[i].window_dict(p))
+                    arr = pa.DictionaryArray.from_arrays(idx, pdict[i])
                 elif c["dtype"] == "dict32":
                     idx = pa.array(fixed[i][b0:b1], type=pa.int32(), mask=mask)
-                    # Rebuild values from the raw offsets/bytes buffers: the device path
-                    # hashes/moves raw bytes, so round-tripping through str would silently
-                    # mutate (or mask) non-UTF8 dictionary bytes.
-                    doff = np.asarray(c["dict_offsets"], dtype=np.int32)
-                    dbuf = np.asarray(c["dict_bytes"], dtype=np.uint8)
-                    values = pa.StringArray.from_buffers(
-                        len(doff) - 1,
-                        pa.py_buffer(doff.tobytes()),
-                        pa.py_buffer(dbuf.tobytes()),
-                        None,
-                    )
+                    values = _utf8_values(pa, c["dict_offsets"], c["dict_bytes"])
                     arr = pa.DictionaryArray.from_arrays(idx, values)
                 elif c["dtype"] == "bool":
                     arr = pa.array(fixed[i][b0:b1].astype(bool), type=pa.bool_(), mask=mask)

@@ -1132,6 +1132,219 @@ extern "C" dd_status dd_bcast_col_meta(const dd_bcast *b, int32_t col, int32_t *
     return DD_OK;
 }
 
+/* ---------------- dictionary GC (dd_dict_gc; kernels in dd_dictgc.hip) ----------------
+ * Device statement of the reference's pre-wire dictionary compaction
+ * (garbage_collect_arrays, src/protocol/grpc/worker_service.rs:363-433). */
+
+struct dd_dict_gc {
+    const dd_partitioner *p = nullptr;
+    int32_t col = -1;
+    uint32_t W = 0, nw = 0, dict_n = 0;
+    int64_t n_rows = 0;
+    int lds = 0;
+    std::vector<int64_t> val_off, byte_off; /* host prefix sums [W+1] */
+    dd_gc_tile *tiles = nullptr;
+    uint32_t *bits = nullptr, *prefix = nullptr; /* [W][nw] */
+    uint32_t *nvals = nullptr;                   /* [W] */
+    uint64_t *nbytes = nullptr;                  /* [W] */
+    uint32_t *flag = nullptr;
+    int64_t *d_off = nullptr; /* device copies: val_off [W+1] then byte_off [W+1] */
+    int32_t *indices = nullptr;
+    int32_t *offs = nullptr;
+    uint8_t *bytes = nullptr;
+    hipEvent_t ev[6] = {}; /* mark: 0-1, rank: 1-2, compact: 3-4, remap: 4-5 */
+    ~dd_dict_gc() {
+        (void)hipFree(tiles);
+        (void)hipFree(bits);
+        (void)hipFree(prefix);
+        (void)hipFree(nvals);
+        (void)hipFree(nbytes);
+        (void)hipFree(flag);
+        (void)hipFree(d_off);
+        (void)hipFree(indices);
+        (void)hipFree(offs);
+        (void)hipFree(bytes);
+        for (auto &e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+extern "C" dd_status dd_dict_gc_run(const dd_partitioner *p, int32_t col, uint32_t n_windows,
+                                    void *stream, dd_dict_gc **out) {
+    if (!p || !out) return set_err(DD_ERR_INVALID, "null argument");
+    if (!p->has_run) return set_err(DD_ERR_INVALID, "partitioner has not run");
+    if (col < 0 || col >= p->batch.n_cols || p->batch.cols[col].dtype != DD_DT_DICT32)
+        return set_err(DD_ERR_INVALID, "dictionary GC needs a dict32 column");
+    if (n_windows == 0 || p->nparts % n_windows != 0)
+        return set_err(DD_ERR_INVALID, "n_windows must be > 0 and divide P_total");
+    const dd_col_desc &cd = p->batch.cols[col];
+    if (cd.dict_n < 0 || cd.dict_n > INT32_MAX || (cd.dict_n > 0 && !cd.dict_offsets))
+        return set_err(DD_ERR_INVALID, "bad dictionary (dict_n / dict_offsets)");
+    const uint64_t nw64 = ((uint64_t)cd.dict_n + 31) / 32;
+    if (nw64 * n_windows > (1ull << 28))
+        return set_err(DD_ERR_UNSUPPORTED,
+                       "dictionary GC bitmap n_windows * ceil(dict_n/32) exceeds 2^28 words "
+                       "(1 GiB): use fewer windows");
+    hipStream_t s = (hipStream_t)stream;
+
+    std::unique_ptr<dd_dict_gc> g(new dd_dict_gc());
+    g->p = p;
+    g->col = col;
+    g->W = n_windows;
+    g->nw = (uint32_t)nw64;
+    g->dict_n = (uint32_t)cd.dict_n;
+    g->n_rows = p->batch.n_rows;
+    /* DD_GC_LDS=0 forces the global tier (A/B knob, read per call) */
+    g->lds = g->nw <= DD_GC_LDS_MAX_WORDS &&
+             !(getenv("DD_GC_LDS") && atoi(getenv("DD_GC_LDS")) == 0);
+    const uint32_t W = g->W, nw = g->nw;
+
+    /* tile table from the host-known row offsets: no tile straddles a window; skewed
+     * windows split into many tiles; empty windows produce none. The LDS tier amortises
+     * staging the nw-word bitmap over >= 8 rows per word. */
+    std::vector<int64_t> roff(p->nparts + 1);
+    dd_status st = dd_partitioner_row_offsets(p, roff.data());
+    if (st != DD_OK) return st;
+    int64_t tile_rows = 8192;
+    if (g->lds) {
+        tile_rows = (((int64_t)nw * 8 + 1023) / 1024) * 1024;
+        if (tile_rows < 4096) tile_rows = 4096;
+        if (tile_rows > 32768) tile_rows = 32768;
+    }
+    const uint32_t ppw = p->nparts / W;
+    std::vector<dd_gc_tile> tiles;
+    for (uint32_t w = 0; w < W; w++) {
+        const int64_t lo = roff[(size_t)w * ppw], hi = roff[(size_t)(w + 1) * ppw];
+        for (int64_t r = lo; r < hi; r += tile_rows)
+            tiles.push_back({r, r + tile_rows < hi ? r + tile_rows : hi, w, 0u});
+    }
+    const int64_t n_tiles = (int64_t)tiles.size();
+    if (n_tiles > INT32_MAX) return set_err(DD_ERR_UNSUPPORTED, "too many GC tiles");
+
+    const size_t words = (size_t)W * nw;
+    HIP_TRY(hipMalloc((void **)&g->tiles, (n_tiles ? n_tiles : 1) * sizeof(dd_gc_tile)));
+    HIP_TRY(hipMalloc((void **)&g->bits, words * 4 + 4));
+    HIP_TRY(hipMalloc((void **)&g->prefix, words * 4 + 4));
+    HIP_TRY(hipMalloc((void **)&g->nvals, (size_t)W * 4));
+    HIP_TRY(hipMalloc((void **)&g->nbytes, (size_t)W * 8));
+    HIP_TRY(hipMalloc((void **)&g->flag, 4));
+    HIP_TRY(hipMalloc((void **)&g->d_off, (size_t)(W + 1) * 16));
+    HIP_TRY(hipMalloc((void **)&g->indices, (size_t)g->n_rows * 4 + 4));
+    for (auto &e : g->ev) HIP_TRY(hipEventCreate(&e));
+    if (n_tiles)
+        HIP_TRY(hipMemcpyAsync(g->tiles, tiles.data(), n_tiles * sizeof(dd_gc_tile),
+                               hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(g->bits, 0, words * 4 + 4, s));
+    HIP_TRY(hipMemsetAsync(g->flag, 0, 4, s));
+
+    const int32_t *idx = (const int32_t *)p->out_data[col];
+    const uint8_t *valid = p->out_valid[col];
+    HIP_TRY(hipEventRecord(g->ev[0], s));
+    HIP_TRY(dd_launch_gc_mark(g->tiles, n_tiles, idx, valid, g->dict_n, nw, g->lds, g->bits,
+                              g->flag, s));
+    HIP_TRY(hipEventRecord(g->ev[1], s));
+    HIP_TRY(dd_launch_gc_rank(g->bits, W, nw, cd.dict_offsets, g->prefix, g->nvals, g->nbytes,
+                              s));
+    HIP_TRY(hipEventRecord(g->ev[2], s));
+
+    /* the one host sync: flag + per-window totals, to size the dictionaries */
+    uint32_t flag_h = 0;
+    std::vector<uint32_t> nvals_h(W);
+    std::vector<uint64_t> nbytes_h(W);
+    HIP_TRY(hipMemcpyAsync(&flag_h, g->flag, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(nvals_h.data(), g->nvals, (size_t)W * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(nbytes_h.data(), g->nbytes, (size_t)W * 8, hipMemcpyDeviceToHost,
+                           s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (flag_h)
+        return set_err(DD_ERR_INVALID, "dictionary GC: a valid row's index is outside "
+                                       "[0, dict_n) (column " + std::to_string(col) + ")");
+    g->val_off.assign(W + 1, 0);
+    g->byte_off.assign(W + 1, 0);
+    for (uint32_t w = 0; w < W; w++) {
+        g->val_off[w + 1] = g->val_off[w] + nvals_h[w];
+        g->byte_off[w + 1] = g->byte_off[w] + (int64_t)nbytes_h[w];
+    }
+    HIP_TRY(hipMalloc((void **)&g->offs, (size_t)(g->val_off[W] + W) * 4));
+    HIP_TRY(hipMalloc((void **)&g->bytes, (size_t)g->byte_off[W] + 1));
+    HIP_TRY(hipMemcpyAsync(g->d_off, g->val_off.data(), (size_t)(W + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(g->d_off + W + 1, g->byte_off.data(), (size_t)(W + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(g->ev[3], s));
+    HIP_TRY(dd_launch_gc_compact(g->bits, g->prefix, W, nw, cd.dict_offsets,
+                                 (const uint8_t *)cd.dict_bytes, g->d_off, g->d_off + W + 1,
+                                 g->offs, g->bytes, s));
+    HIP_TRY(hipEventRecord(g->ev[4], s));
+    HIP_TRY(dd_launch_gc_remap(g->tiles, n_tiles, idx, valid, g->dict_n, nw, g->lds, g->bits,
+                               g->prefix, g->indices, s));
+    HIP_TRY(hipEventRecord(g->ev[5], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = g.release();
+    return DD_OK;
+}
+
+extern "C" void dd_dict_gc_destroy(dd_dict_gc *g) { delete g; }
+extern "C" int32_t dd_dict_gc_col(const dd_dict_gc *g) { return g ? g->col : -1; }
+extern "C" uint32_t dd_dict_gc_n_windows(const dd_dict_gc *g) { return g ? g->W : 0; }
+extern "C" const int32_t *dd_dict_gc_indices(const dd_dict_gc *g) { return g->indices; }
+extern "C" const int32_t *dd_dict_gc_dict_offsets(const dd_dict_gc *g) { return g->offs; }
+extern "C" const uint8_t *dd_dict_gc_dict_bytes(const dd_dict_gc *g) { return g->bytes; }
+
+extern "C" dd_status dd_dict_gc_counts(const dd_dict_gc *g, int64_t *val_off,
+                                       int64_t *byte_off) {
+    if (!g || !val_off || !byte_off) return set_err(DD_ERR_INVALID, "null argument");
+    memcpy(val_off, g->val_off.data(), g->val_off.size() * 8);
+    memcpy(byte_off, g->byte_off.data(), g->byte_off.size() * 8);
+    return DD_OK;
+}
+
+extern "C" dd_status dd_dict_gc_kernel_ms(const dd_dict_gc *g, float out_ms[4]) {
+    if (!g || !out_ms) return set_err(DD_ERR_INVALID, "null argument");
+    HIP_TRY(hipEventSynchronize(g->ev[5]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[0], g->ev[0], g->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[1], g->ev[1], g->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[2], g->ev[3], g->ev[4]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[3], g->ev[4], g->ev[5]));
+    return DD_OK;
+}
+
+/* rebase with host tables: uploads them, runs k_gc_rebase, syncs, frees (every path) */
+static dd_status dd_rebase_run(const int32_t *in, int64_t n, const int64_t *host_seg_off,
+                               const int32_t *host_bases, int32_t n_seg, int32_t skew,
+                               int32_t *out, hipStream_t s) {
+    if (n <= 0 || n_seg <= 0) return DD_OK;
+    int64_t *d_seg = nullptr;
+    int32_t *d_base = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_seg, (size_t)(n_seg + 1) * 8));
+    hipError_t he = hipMalloc((void **)&d_base, (size_t)n_seg * 4);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(d_seg, host_seg_off, (size_t)(n_seg + 1) * 8,
+                            hipMemcpyHostToDevice, s);
+    if (he == hipSuccess)
+        he = hipMemcpyAsync(d_base, host_bases, (size_t)n_seg * 4, hipMemcpyHostToDevice, s);
+    if (he == hipSuccess) he = dd_launch_gc_rebase(in, n, d_seg, d_base, n_seg, skew, out, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    (void)hipFree(d_seg);
+    (void)hipFree(d_base);
+    if (he != hipSuccess)
+        return set_err(DD_ERR_HIP, std::string("dict rebase: ") + hipGetErrorString(he));
+    return DD_OK;
+}
+
+extern "C" dd_status dd_dict_rebase(const int32_t *in, int64_t n, const int64_t *host_seg_off,
+                                    const int32_t *host_bases, int32_t n_seg, int32_t *out,
+                                    void *stream) {
+    if (!host_seg_off || !host_bases || n < 0 || n_seg <= 0 || (n > 0 && (!in || !out)))
+        return set_err(DD_ERR_INVALID, "dd_dict_rebase: null or negative argument");
+    if (host_seg_off[0] != 0 || host_seg_off[n_seg] != n)
+        return set_err(DD_ERR_INVALID, "dd_dict_rebase: segments must cover [0, n)");
+    for (int32_t q = 0; q < n_seg; q++)
+        if (host_seg_off[q + 1] < host_seg_off[q])
+            return set_err(DD_ERR_INVALID, "dd_dict_rebase: segment offsets must ascend");
+    return dd_rebase_run(in, n, host_seg_off, host_bases, n_seg, 0, out, (hipStream_t)stream);
+}
+
 
 struct dd_exchanged {
     int32_t n_cols = 0;
@@ -1146,11 +1359,24 @@ struct dd_exchanged {
     void *data[DD_MAX_COLS] = {};
     uint8_t *valid[DD_MAX_COLS] = {};
     uint32_t *lengths[DD_MAX_COLS] = {};
+    /* GC'd dict32 columns (dd_exchange_run_gc): the received dictionaries, concatenated in
+     * producer-rank order; dict_raw is the per-producer offsets arrays as received */
+    int64_t dict_n[DD_MAX_COLS];
+    int32_t *dict_off[DD_MAX_COLS] = {};
+    int32_t *dict_raw[DD_MAX_COLS] = {};
+    uint8_t *dict_bytes[DD_MAX_COLS] = {};
+    std::vector<std::vector<int64_t>> dict_vals; /* per col: [nranks] values per producer */
     float ms = 0;
     int64_t egress = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
+    dd_exchanged() {
+        for (auto &d : dict_n) d = -1;
+    }
     ~dd_exchanged() {
         for (int i = 0; i < DD_MAX_COLS; i++) {
+            if (dict_off[i]) (void)hipFreeAsync(dict_off[i], alloc_stream);
+            if (dict_raw[i]) (void)hipFreeAsync(dict_raw[i], alloc_stream);
+            if (dict_bytes[i]) (void)hipFreeAsync(dict_bytes[i], alloc_stream);
             if (data[i]) (void)hipFreeAsync(data[i], alloc_stream);
             if (valid[i]) (void)hipFreeAsync(valid[i], alloc_stream);
             if (lengths[i]) (void)hipFreeAsync(lengths[i], alloc_stream);
@@ -1160,9 +1386,11 @@ struct dd_exchanged {
     }
 };
 
-extern "C" dd_status dd_exchange_run(dd_comm *c, const dd_partitioner *p, void *stream,
-                                     dd_exchanged **out) {
-    if (!c || !p || !out) return set_err(DD_ERR_INVALID, "null argument");
+/* shared body of dd_exchange_run (n_gcs == 0) and dd_exchange_run_gc */
+static dd_status dd_exchange_impl(dd_comm *c, const dd_partitioner *p, dd_dict_gc *const *gcs,
+                                  int32_t n_gcs, void *stream, dd_exchanged **out) {
+    if (!c || !p || !out || n_gcs < 0 || (n_gcs > 0 && !gcs))
+        return set_err(DD_ERR_INVALID, "null argument");
     if (!p->has_run) return set_err(DD_ERR_INVALID, "partitioner has not run");
     if (p->nparts % c->nranks != 0)
         return set_err(DD_ERR_INVALID, "P_total must be nranks * partitions-per-consumer "
@@ -1171,11 +1399,30 @@ extern "C" dd_status dd_exchange_run(dd_comm *c, const dd_partitioner *p, void *
     const uint32_t P = p->nparts / c->nranks;
     const int R = c->nranks;
     const int nvar = p->ka.n_var;
+    /* gc_of[col]: the GC covering a dict32 column, or null (crosses as plain indices) */
+    const dd_dict_gc *gc_of[DD_MAX_COLS] = {};
+    for (int32_t gi = 0; gi < n_gcs; gi++) {
+        const dd_dict_gc *g = gcs[gi];
+        if (!g || g->p != p || g->W != (uint32_t)R || gc_of[g->col])
+            return set_err(DD_ERR_INVALID, "each dictionary GC must belong to this "
+                                           "partitioner, have n_windows == nranks and "
+                                           "cover its column once");
+        gc_of[g->col] = g;
+    }
 
     /* 1) size matrix: my per-partition row counts (+ per var col byte counts), allgathered.
-     * meta layout per rank: [P_total rows][nvar * P_total bytes] (u64) */
-    const size_t meta_n = (size_t)p->nparts * (1 + nvar);
+     * meta layout per rank: [P_total rows][nvar * P_total bytes] (u64), then per GC'd
+     * column, in gcs[] order, [R value counts][R byte counts] of its R windows */
+    const size_t meta_gc0 = (size_t)p->nparts * (1 + nvar);
+    const size_t meta_n = meta_gc0 + (size_t)n_gcs * 2 * R;
     std::vector<int64_t> my_meta(meta_n);
+    for (int32_t gi = 0; gi < n_gcs; gi++)
+        for (int j = 0; j < R; j++) {
+            my_meta[meta_gc0 + (size_t)gi * 2 * R + j] =
+                gcs[gi]->val_off[j + 1] - gcs[gi]->val_off[j];
+            my_meta[meta_gc0 + (size_t)gi * 2 * R + R + j] =
+                gcs[gi]->byte_off[j + 1] - gcs[gi]->byte_off[j];
+        }
     std::vector<int64_t> off_h(p->nparts + 1);
     dd_status st = dd_partitioner_row_offsets(p, off_h.data());
     if (st != DD_OK) return st;
@@ -1192,6 +1439,18 @@ extern "C" dd_status dd_exchange_run(dd_comm *c, const dd_partitioner *p, void *
         dd_status ms = dd_meta_allgather(c, my_meta, all_meta, s);
         if (ms != DD_OK) return ms;
     }
+
+    /* a consumer's concatenated dictionary keeps i32 offsets. Checked for EVERY consumer
+     * from the allgathered matrix, so all ranks take the same exit before the collective */
+    for (int32_t gi = 0; gi < n_gcs; gi++)
+        for (int j = 0; j < R; j++) {
+            int64_t tb = 0;
+            for (int r = 0; r < R; r++)
+                tb += all_meta[(size_t)r * meta_n + meta_gc0 + (size_t)gi * 2 * R + R + j];
+            if (tb > INT32_MAX)
+                return set_err(DD_ERR_UNSUPPORTED, "received dictionary bytes exceed "
+                                                   "INT32_MAX (i32 Arrow offsets)");
+        }
 
     std::unique_ptr<dd_exchanged> e_own(new dd_exchanged()); /* freed on error returns */
     dd_exchanged *e = e_own.get();
@@ -1251,6 +1510,28 @@ extern "C" dd_status dd_exchange_run(dd_comm *c, const dd_partitioner *p, void *
                 return fail(DD_ERR_HIP, "recv alloc (validity)");
         }
     }
+    /* received dictionaries: per GC'd column, values/bytes per producer for MY window */
+    e->dict_vals.assign(p->batch.n_cols, {});
+    std::vector<std::vector<int64_t>> dict_rb(p->batch.n_cols); /* bytes per producer */
+    for (int32_t gi = 0; gi < n_gcs; gi++) {
+        const int ci = gcs[gi]->col;
+        e->dict_vals[ci].assign(R, 0);
+        dict_rb[ci].assign(R, 0);
+        int64_t tv = 0, tb = 0;
+        for (int r = 0; r < R; r++) {
+            const size_t b = (size_t)r * meta_n + meta_gc0 + (size_t)gi * 2 * R;
+            tv += e->dict_vals[ci][r] = all_meta[b + c->rank];
+            tb += dict_rb[ci][r] = all_meta[b + R + c->rank];
+        }
+        e->dict_n[ci] = tv;
+        if (hipMallocAsync((void **)&e->dict_raw[ci], (size_t)(tv + R) * 4, e->alloc_stream) !=
+                hipSuccess ||
+            hipMallocAsync((void **)&e->dict_off[ci], (size_t)(tv + 1) * 4, e->alloc_stream) !=
+                hipSuccess ||
+            hipMallocAsync((void **)&e->dict_bytes[ci], (size_t)tb + 1, e->alloc_stream) !=
+                hipSuccess)
+            return fail(DD_ERR_HIP, "recv alloc (dictionary)");
+    }
 
     if (hipStreamSynchronize(e->alloc_stream) != hipSuccess) /* allocations ready */
         return fail(DD_ERR_HIP, "pool stream sync");
@@ -1271,9 +1552,11 @@ extern "C" dd_status dd_exchange_run(dd_comm *c, const dd_partitioner *p, void *
             const dd_kcol &kc = p->ka.cols[ci];
             if (kc.elem > 0) {
                 int64_t sb = (srow1 - srow0) * kc.elem;
+                /* a GC'd column sends its window-local indices, not the partitioner's */
+                const uint8_t *src = gc_of[ci] ? (const uint8_t *)gc_of[ci]->indices
+                                               : (const uint8_t *)p->out_data[ci];
                 if (sb > 0)
-                    NCCL_TRY(ncclSend((const uint8_t *)p->out_data[ci] + srow0 * kc.elem, sb,
-                                      ncclUint8, j, c->comm, s));
+                    NCCL_TRY(ncclSend(src + srow0 * kc.elem, sb, ncclUint8, j, c->comm, s));
                 int64_t rb = rrows * kc.elem;
                 if (rb > 0)
                     NCCL_TRY(ncclRecv((uint8_t *)e->data[ci] + rrow0 * kc.elem, rb, ncclUint8,
@@ -1308,13 +1591,87 @@ extern "C" dd_status dd_exchange_run(dd_comm *c, const dd_partitioner *p, void *
                     NCCL_TRY(ncclRecv(e->valid[ci] + rrow0, rrows, ncclUint8, j, c->comm, s));
                 if (j != c->rank) e->egress += srow1 - srow0;
             }
+            if (const dd_dict_gc *g = gc_of[ci]) {
+                /* window j's dictionary: nvals+1 zero-based offsets and its bytes, each one
+                 * contiguous slice; received producer-major */
+                const int64_t sv = g->val_off[j + 1] - g->val_off[j];
+                const int64_t sbb = g->byte_off[j + 1] - g->byte_off[j];
+                NCCL_TRY(ncclSend(g->offs + g->val_off[j] + j, (sv + 1) * 4, ncclUint8, j,
+                                  c->comm, s));
+                if (sbb > 0)
+                    NCCL_TRY(ncclSend(g->bytes + g->byte_off[j], sbb, ncclUint8, j, c->comm, s));
+                int64_t rv0 = 0, rb0 = 0;
+                for (int r = 0; r < j; r++) {
+                    rv0 += e->dict_vals[ci][r];
+                    rb0 += dict_rb[ci][r];
+                }
+                NCCL_TRY(ncclRecv(e->dict_raw[ci] + rv0 + j, (e->dict_vals[ci][j] + 1) * 4,
+                                  ncclUint8, j, c->comm, s));
+                if (dict_rb[ci][j] > 0)
+                    NCCL_TRY(ncclRecv(e->dict_bytes[ci] + rb0, dict_rb[ci][j], ncclUint8, j,
+                                      c->comm, s));
+                if (j != c->rank) e->egress += (sv + 1) * 4 + sbb;
+            }
         }
     }
     NCCL_TRY(ncclGroupEnd());
     HIP_TRY(hipEventRecord(e->e1, s));
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipEventElapsedTime(&e->ms, e->e0, e->e1));
+
+    /* after the collective: rebase producer r's indices by the values received from
+     * producers < r, and splice the R zero-based offsets arrays into one [dict_n + 1] */
+    for (int32_t gi = 0; gi < n_gcs; gi++) {
+        const int ci = gcs[gi]->col;
+        std::vector<int64_t> seg(R + 1, 0);
+        std::vector<int32_t> vbase(R, 0), bbase(R, 0);
+        for (int r = 0; r < R; r++) seg[r + 1] = seg[r] + recv_rows_per_producer[r];
+        for (int r = 1; r < R; r++) {
+            vbase[r] = vbase[r - 1] + (int32_t)e->dict_vals[ci][r - 1];
+            bbase[r] = bbase[r - 1] + (int32_t)dict_rb[ci][r - 1];
+        }
+        st = dd_rebase_run((const int32_t *)e->data[ci], e->total_rows, seg.data(),
+                           vbase.data(), R, 0, (int32_t *)e->data[ci], s);
+        if (st != DD_OK) return st;
+        /* offsets: output segment r = producer r's first nvals entries (its closing entry
+         * equals the next producer's rebased 0); the last segment keeps its closing entry */
+        for (int r = 0; r < R; r++) seg[r + 1] = seg[r] + e->dict_vals[ci][r];
+        seg[R] += 1;
+        st = dd_rebase_run(e->dict_raw[ci], e->dict_n[ci] + 1, seg.data(), bbase.data(), R, 1,
+                           e->dict_off[ci], s);
+        if (st != DD_OK) return st;
+        (void)hipFreeAsync(e->dict_raw[ci], e->alloc_stream); /* spliced (rebase synced) */
+        e->dict_raw[ci] = nullptr;
+    }
     *out = e_own.release();
+    return DD_OK;
+}
+
+extern "C" dd_status dd_exchange_run(dd_comm *c, const dd_partitioner *p, void *stream,
+                                     dd_exchanged **out) {
+    return dd_exchange_impl(c, p, nullptr, 0, stream, out);
+}
+
+extern "C" dd_status dd_exchange_run_gc(dd_comm *c, const dd_partitioner *p,
+                                        dd_dict_gc *const *gcs, int32_t n_gcs, void *stream,
+                                        dd_exchanged **out) {
+    return dd_exchange_impl(c, p, gcs, n_gcs, stream, out);
+}
+
+extern "C" int64_t dd_exchanged_dict_n(const dd_exchanged *e, int32_t c) {
+    return (e && c >= 0 && c < e->n_cols) ? e->dict_n[c] : -1;
+}
+extern "C" const int32_t *dd_exchanged_dict_offsets(const dd_exchanged *e, int32_t c) {
+    return (e && c >= 0 && c < e->n_cols) ? e->dict_off[c] : nullptr;
+}
+extern "C" const void *dd_exchanged_dict_bytes(const dd_exchanged *e, int32_t c) {
+    return (e && c >= 0 && c < e->n_cols) ? e->dict_bytes[c] : nullptr;
+}
+extern "C" dd_status dd_exchanged_dict_counts(const dd_exchanged *e, int32_t c,
+                                              int64_t *vals_per_producer) {
+    if (!e || !vals_per_producer || c < 0 || c >= e->n_cols || e->dict_n[c] < 0)
+        return set_err(DD_ERR_INVALID, "column did not cross with a dictionary GC");
+    memcpy(vals_per_producer, e->dict_vals[c].data(), e->dict_vals[c].size() * 8);
     return DD_OK;
 }
 

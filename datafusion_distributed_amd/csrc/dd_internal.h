@@ -65,9 +65,38 @@ struct dd_kargs {
     dd_kcol cols[DD_KMAX_COLS];
 };
 
+/* dictionary GC (dd_dictgc.hip): one workgroup per row tile; a tile never straddles a
+ * window boundary */
+struct dd_gc_tile {
+    int64_t row_lo, row_hi; /* partition-major output rows [row_lo, row_hi) */
+    uint32_t window;
+    uint32_t pad;
+};
+#define DD_GC_LDS_THREADS 1024 /* LDS tier: 16 waves share one staged bitmap */
+#define DD_GC_GLB_THREADS 256
+#define DD_GC_LDS_MAX_WORDS 16384u /* 64 KiB bitmap = dict_n <= 524288 */
+
 #include "dd_shuffle.h" /* dd_status for dd_set_error */
 
 extern "C" {
+hipError_t dd_launch_gc_mark(const dd_gc_tile *tiles, int64_t n_tiles, const int32_t *idx,
+                             const uint8_t *valid, uint32_t dict_n, uint32_t nw, int lds,
+                             uint32_t *bits, uint32_t *flag, hipStream_t s);
+hipError_t dd_launch_gc_rank(const uint32_t *bits, uint32_t n_windows, uint32_t nw,
+                             const int32_t *dict_offsets, uint32_t *prefix, uint32_t *nvals,
+                             uint64_t *nbytes, hipStream_t s);
+hipError_t dd_launch_gc_compact(const uint32_t *bits, const uint32_t *prefix,
+                                uint32_t n_windows, uint32_t nw, const int32_t *dict_offsets,
+                                const uint8_t *dict_bytes, const int64_t *val_off,
+                                const int64_t *byte_off, int32_t *offs, uint8_t *out_bytes,
+                                hipStream_t s);
+hipError_t dd_launch_gc_remap(const dd_gc_tile *tiles, int64_t n_tiles, const int32_t *idx,
+                              const uint8_t *valid, uint32_t dict_n, uint32_t nw, int lds,
+                              const uint32_t *bits, const uint32_t *prefix, int32_t *out,
+                              hipStream_t s);
+hipError_t dd_launch_gc_rebase(const int32_t *in, int64_t n, const int64_t *seg_off,
+                               const int32_t *bases, int32_t n_seg, int32_t skew,
+                               int32_t *out, hipStream_t s);
 dd_status dd_set_error(dd_status s, const char *msg); /* thread-local dd_last_error */
 hipError_t dd_launch_dict_hashes(const uint8_t *bytes, const int32_t *offsets, int64_t n,
                                  uint64_t *out, hipStream_t s);

@@ -178,6 +178,71 @@ dd_status dd_exchanged_byte_counts(const dd_exchanged *e, int32_t col, int64_t *
  * this rank to OTHER ranks (xGMI egress) */
 dd_status dd_exchanged_stats(const dd_exchanged *e, float *ms, int64_t *egress_bytes);
 
+/* ---------------- dictionary GC (compact + resend dictionaries) ----------------
+ * The reference compacts every dictionary column to the values a batch references before
+ * it goes on the wire and resends the compacted dictionary with the batch
+ * (garbage_collect_arrays + DictionaryHandling::Resend,
+ * src/protocol/grpc/worker_service.rs:363-433). Here the unit is a WINDOW: the P_total
+ * partitions are cut into n_windows contiguous ranges and each window gets its own
+ * compacted dictionary and window-local indices (normative). n_windows =
+ * nranks gives one dictionary per consumer (dd_exchange_run_gc); n_windows = P_total gives
+ * one per partition (the Arrow boundary, the reference's per-batch granularity). */
+
+typedef struct dd_dict_gc dd_dict_gc; /* opaque: bitmaps, remapped indices, dictionaries */
+
+/* Runs mark/rank/compact/remap for dict32 column `col` of a run partitioner. Synchronous
+ * (one host sync to size the dictionaries); `stream` must be ordered after the
+ * partitioner's run. The partitioner's own output is not modified
+ * and must outlive the GC object. A valid row whose index is outside [0, dict_n) is never
+ * dereferenced: DD_ERR_INVALID (worker_service.rs:363-433 is the seam). */
+dd_status dd_dict_gc_run(const dd_partitioner *p, int32_t col, uint32_t n_windows,
+                         void *stream, dd_dict_gc **out);
+/* worker_service.rs:363-433: releases the GC'd dictionaries and indices */
+void dd_dict_gc_destroy(dd_dict_gc *g);
+/* worker_service.rs:363-433: which column / how many windows this GC covers */
+int32_t dd_dict_gc_col(const dd_dict_gc *g);
+uint32_t dd_dict_gc_n_windows(const dd_dict_gc *g);
+/* device i32[n_rows]: window-local indices, partition-major like the partitioner's output
+ * (0 for null rows; the validity buffer stays the partitioner's) —
+ * worker_service.rs:363-433 ships these as the batch's dictionary keys */
+const int32_t *dd_dict_gc_indices(const dd_dict_gc *g);
+/* host prefix sums, [n_windows+1] each: values and bytes per window
+ * (worker_service.rs:363-433: the size of each resent dictionary) */
+dd_status dd_dict_gc_counts(const dd_dict_gc *g, int64_t *val_off, int64_t *byte_off);
+/* device: window w's zero-based offsets array (nvals_w+1 entries) starts at element
+ * val_off[w] + w; its bytes start at byte_off[w] — each window is a ready Arrow utf8 array
+ * and one contiguous send slice (worker_service.rs:363-433: the resent dictionary) */
+const int32_t *dd_dict_gc_dict_offsets(const dd_dict_gc *g);
+const uint8_t *dd_dict_gc_dict_bytes(const dd_dict_gc *g);
+/* hipEvent durations of the last run in ms: mark, rank, compact, remap (the device cost
+ * of the worker_service.rs:363-433 GC step) */
+dd_status dd_dict_gc_kernel_ms(const dd_dict_gc *g, float out_ms[4]);
+
+/* dd_exchange_run that also carries dictionaries (worker_service.rs:363-433, Resend):
+ * every GC in gcs[] must belong to `p` and have n_windows == nranks. A GC'd column's
+ * indices are sent from the GC's buffer, and window j's compacted dictionary goes to rank
+ * j in the same grouped send/recv. On the consumer the nranks received dictionaries are
+ * concatenated in producer-rank order and the indices rebased, so the column is one
+ * decodable dictionary array. n_gcs == 0 is dd_exchange_run; a dict32 column without a GC
+ * crosses as plain i32 indices, as before. */
+dd_status dd_exchange_run_gc(dd_comm *c, const dd_partitioner *p, dd_dict_gc *const *gcs,
+                             int32_t n_gcs, void *stream, dd_exchanged **out);
+/* received dictionary of a GC'd column (worker_service.rs:363-433 on the consumer side):
+ * number of values (-1 when the column crossed without a GC), device i32[dict_n+1]
+ * zero-based offsets, device value bytes, and host values-per-producer [nranks] */
+int64_t dd_exchanged_dict_n(const dd_exchanged *e, int32_t col);
+const int32_t *dd_exchanged_dict_offsets(const dd_exchanged *e, int32_t col);
+const void *dd_exchanged_dict_bytes(const dd_exchanged *e, int32_t col);
+dd_status dd_exchanged_dict_counts(const dd_exchanged *e, int32_t col,
+                                   int64_t *vals_per_producer);
+
+/* device helper, also used internally after the collective (worker_service.rs:363-433's
+ * consumer half): out[i] = in[i] + bases[s] for seg_off[s] <= i < seg_off[s+1];
+ * seg_off[0] == 0, seg_off[n_seg] == n. in == out is allowed. Synchronous. */
+dd_status dd_dict_rebase(const int32_t *in, int64_t n, const int64_t *host_seg_off,
+                         const int32_t *host_bases, int32_t n_seg, int32_t *out,
+                         void *stream);
+
 /* ---------------- coalesce (N->M task coalesce, no repartition) ----------------
  * Data plane for NetworkCoalesceExec (src/execution_plans/network_coalesce.rs:24-70):
  * consumer rank t receives the WHOLE partitioned output of every producer rank in its
