@@ -533,15 +533,35 @@ AGG_OPS = {"sum_f64": 0, "count": 1, "sum_i64": 2, "min_f64": 3, "max_f64": 4,
            "min_i64": 5, "max_i64": 6}
 
 
+def partial_reduce_geometry(n_rows):
+    """Launch geometry partial_reduce uses for an n_rows batch (no device needed):
+    {"table_slots", "probe_limit", "nblocks", "chunk_rows"}."""
+    slots = ctypes.c_int32()
+    probe = ctypes.c_int32()
+    nblocks = ctypes.c_int64()
+    chunk = ctypes.c_int64()
+    _check(lib().dd_partial_reduce_geometry(
+        ctypes.c_int64(n_rows), ctypes.byref(slots), ctypes.byref(probe),
+        ctypes.byref(nblocks), ctypes.byref(chunk)))
+    return {"table_slots": int(slots.value), "probe_limit": int(probe.value),
+            "nblocks": int(nblocks.value), "chunk_rows": int(chunk.value)}
+
+
 def partial_reduce(batch: DeviceBatch, key_idx, aggs):
     """GPU partial aggregation below the shuffle (dd_partial_reduce_run).
 
-    aggs: list of (col_index_or_None, op) with op in {"sum_f64", "count", "sum_i64"}.
-    Returns {"keys": u64[n, nk] canonical bits, "keynull": u32[n] per-key null bitmask,
-    "aggs": f64[n, na], "nn": u64[n, na] non-null input counts} — integer aggregates
-    (count / sum_i64) are bit-cast in the f64 slots (view with .view(np.int64)). May
-    contain duplicate groups (partial semantics). The final merge sums "nn" per group and
-    emits NULL for an aggregate whose total non-null count is 0 (DataFusion semantics).
+    key_idx: 1..4 key columns, fixed-width or dict32 (grouped by dictionary index).
+    aggs: 1..4 of (col_index_or_None, op) with op in AGG_OPS: "count" (every row, column
+    ignored), "sum_f64", "sum_i64" (wraps mod 2^64), "min_f64"/"max_f64" (IEEE totalOrder
+    on the bit pattern: sign-set NaN < -inf < -0.0 < +0.0 < +inf < sign-clear NaN),
+    "min_i64"/"max_i64". Every op but count skips NULL inputs.
+    Returns {"keys": u64[n, nk] canonical bits (0 for a NULL key component), "keynull":
+    u32[n] per-key null bitmask, "aggs": f64[n, na], "nn": u64[n, na] non-null input
+    counts} — integer aggregates (count / sum_i64 / min_i64 / max_i64) are bit-cast in
+    the f64 slots (view with .view(np.int64)). May contain duplicate groups (partial
+    semantics). The final merge sums "nn" per group, skips the value of a partial whose
+    nn is 0 (it holds the op identity), and emits NULL for an aggregate whose total
+    non-null count is 0 (DataFusion semantics).
     """
     nk = len(key_idx)
     na = len(aggs)

@@ -1728,6 +1728,27 @@ struct dd_reducer {
     }
 };
 
+/* launch geometry of k_partial_reduce: the one place this arithmetic lives (used by the
+ * run below and reported by dd_partial_reduce_geometry) */
+static void dd_reduce_geometry(int64_t n, int64_t *nblocks, int64_t *chunk) {
+    int64_t nb = (n + DD_R_BLOCK_ROWS - 1) / DD_R_BLOCK_ROWS;
+    if (nb < DD_R_MIN_BLOCKS) nb = DD_R_MIN_BLOCKS;
+    if (nb > DD_R_MAX_BLOCKS) nb = DD_R_MAX_BLOCKS;
+    *nblocks = nb;
+    *chunk = (n + nb - 1) / nb;
+}
+
+extern "C" dd_status dd_partial_reduce_geometry(int64_t n_rows, int32_t *table_slots,
+                                                int32_t *probe_limit, int64_t *nblocks,
+                                                int64_t *chunk_rows) {
+    if (n_rows < 0 || !table_slots || !probe_limit || !nblocks || !chunk_rows)
+        return set_err(DD_ERR_INVALID, "null argument or negative row count");
+    *table_slots = DD_R_CAP;
+    *probe_limit = DD_R_PROBE;
+    dd_reduce_geometry(n_rows, nblocks, chunk_rows);
+    return DD_OK;
+}
+
 extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
                                            const int32_t *key_cols, int32_t n_keys,
                                            const int32_t *agg_cols, const int32_t *agg_ops,
@@ -1778,11 +1799,9 @@ extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
         kc.offsets = cd.offsets;
     }
 
-    int64_t nblocks = (n + 16383) / 16384;
-    if (nblocks < 8) nblocks = 8;
-    if (nblocks > 1024) nblocks = 1024;
-    const int64_t chunk = (n + nblocks - 1) / nblocks;
-    const int64_t max_rows = n + nblocks * 1024 + 1; /* spill worst case + table flush */
+    int64_t nblocks, chunk;
+    dd_reduce_geometry(n, &nblocks, &chunk);
+    const int64_t max_rows = n + nblocks * DD_R_CAP + 1; /* spill worst case + table flush */
 
     auto r = new dd_reducer();
     r->n_keys = n_keys;

@@ -14,6 +14,14 @@
 #define DD_SCAN_RANGES 64
 #define DD_STAGE_MAXC 8 /* staged-path column cap (register prefetch arrays) */
 
+/* partial-reduce geometry (dd_reduce.hip kernel + dd_host.cpp launch/allocation; reported
+ * by dd_partial_reduce_geometry so tests never mirror these literals) */
+#define DD_R_CAP 1024        /* LDS table slots per block */
+#define DD_R_PROBE 64        /* bounded linear probe; then spill */
+#define DD_R_BLOCK_ROWS 16384 /* target rows per block */
+#define DD_R_MIN_BLOCKS 8
+#define DD_R_MAX_BLOCKS 1024
+
 /* dtype codes mirror dd_dtype in include/dd_shuffle.h */
 enum {
     DD_KDT_U8 = 1,

@@ -16,8 +16,8 @@
  * singleton groups (sum = value, count = 1) — correct for any cardinality, fast for the
  * low-cardinality keys partial-reduce targets (q1: 6 groups).
  *
- * Coverage: fixed-width key columns (nullable), aggregate ops
- * sum(f64) / sum(i64) / count(*) / min / max.
+ * Coverage: fixed-width and dict32-by-index key columns (nullable), aggregate ops
+ * sum(f64) / sum(i64, wrapping) / count(*) / min / max (contract: include/dd_shuffle.h).
  *
  * NULL semantics: each aggregate carries a NON-NULL INPUT COUNT in the partial state
  * (out_nn), so the downstream final merge can emit NULL for a group whose inputs were all
@@ -32,13 +32,14 @@
 
 #define RWAVE 64
 #define R_THREADS 256
-#define R_CAP 1024      /* table slots per block */
-#define R_PROBE 64      /* bounded probe; then spill */
+#define R_CAP DD_R_CAP     /* table slots per block (dd_internal.h) */
+#define R_PROBE DD_R_PROBE /* bounded probe; then spill */
 
 /* agg op codes come from include/dd_shuffle.h (via dd_internal.h) */
 
-/* order-preserving f64 <-> u64 map (IEEE total order; NaN sorts above +inf, matching
- * Arrow's max semantics): x >= 0 -> bits | sign, x < 0 -> ~bits */
+/* order-preserving f64 <-> u64 map (IEEE-754 totalOrder on the bit pattern: a sign-clear
+ * NaN sorts above +inf, a sign-set NaN below -inf): sign clear -> bits | sign,
+ * sign set -> ~bits */
 __device__ __forceinline__ uint64_t dd_f64_key(double v) {
     uint64_t b = __double_as_longlong(v);
     return (b & 0x8000000000000000ULL) ? ~b : (b | 0x8000000000000000ULL);

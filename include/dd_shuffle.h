@@ -388,17 +388,40 @@ void dd_ipc_reader_destroy(dd_ipc_reader *r);
  * partial_reduce_below_network_shuffles.rs; `distributed.partial_reduce`,
  * distributed_config.rs:50-54): a mode=Partial aggregate run before dd_partition so the
  * exchange moves per-group partials. May emit duplicate groups (one per block); the
- * downstream final aggregate merges them. Fixed-width keys (<=4), aggregate ops below. */
+ * downstream final aggregate merges them. Up to 4 key columns: fixed-width (u8, i16,
+ * i32, i64, f32, f64, bool) or dict32 grouped BY INDEX (utf8 keys are unsupported). Float
+ * keys are canonicalised like the row hash (-0.0 -> +0.0, every NaN -> one quiet NaN).
+ * Duplicate dictionary values under different indices yield separate partial groups,
+ * which the final aggregate merges by value. Up to 4 aggregates, ops below.
+ *
+ * Aggregate contract (every op but COUNT skips NULL inputs):
+ *  - Each output row carries, per aggregate, the NON-NULL INPUT COUNT `nn`
+ *    (dd_reducer_fetch_nn). The final merge sums nn per group; a total of 0 means the
+ *    merged aggregate is SQL NULL. The value slot of a partial with nn == 0 holds the op
+ *    identity and must be skipped by a min/max merge.
+ *  - SUM_I64 wraps modulo 2^64 (two's complement), like the u64 atomic add behind it.
+ *  - MIN_F64 / MAX_F64 order by IEEE-754 totalOrder on the bit pattern:
+ *    -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN. A sign-set NaN (e.g. the
+ *    0xfff8... that x86 produces for inf - inf) therefore sorts BELOW -inf; only a
+ *    sign-clear NaN sorts above +inf. NaN payloads and the sign of zero are preserved.
+ *  - SUM_F64 adds in an unspecified order (floating-point atomics). */
 
 typedef struct dd_reducer dd_reducer;
 
-#define DD_AGG_SUM_F64 0 /* sum of an f64 column (nulls skipped) */
-#define DD_AGG_COUNT 1   /* count(*) (agg_col ignored) */
-#define DD_AGG_SUM_I64 2 /* sum of an i64 column (nulls skipped) */
-#define DD_AGG_MIN_F64 3 /* min/max skip nulls; NaN sorts above +inf (Arrow semantics); */
-#define DD_AGG_MAX_F64 4 /* an all-null group yields the identity (0 / +-extreme), not   */
-#define DD_AGG_MIN_I64 5 /* SQL NULL — pair with count(col) downstream to reconstruct    */
-#define DD_AGG_MAX_I64 6 /* null results */
+#define DD_AGG_SUM_F64 0 /* sum of an f64 column */
+#define DD_AGG_COUNT 1   /* count(*): every row, agg_col ignored; nn == count, never NULL */
+#define DD_AGG_SUM_I64 2 /* wrapping sum of an i64 column */
+#define DD_AGG_MIN_F64 3 /* totalOrder min / max of an f64 column */
+#define DD_AGG_MAX_F64 4
+#define DD_AGG_MIN_I64 5 /* signed min / max of an i64 column */
+#define DD_AGG_MAX_I64 6
+
+/* Launch geometry dd_partial_reduce_run uses for an n_rows batch: LDS table slots per
+ * block, probe limit before a row spills as a singleton group, block count and rows per
+ * block (the last block may be ragged or empty). Needs no device. */
+dd_status dd_partial_reduce_geometry(int64_t n_rows, int32_t *table_slots,
+                                     int32_t *probe_limit, int64_t *nblocks,
+                                     int64_t *chunk_rows);
 
 dd_status dd_partial_reduce_run(const dd_batch_desc *batch, const int32_t *key_cols,
                                 int32_t n_keys, const int32_t *agg_cols,

@@ -65,18 +65,19 @@ def test_q1_pipeline_partial_reduce_shuffle_final():
     sp = ex.col_data(3)["data"]
     cn = ex.col_data(4)["data"]
     final = {}
+    home = {}  # group key -> the partition it was first seen in
     for p in range(P):
         lo, hi = off[p], off[p + 1]
-        seen_here = set()
         for i in range(lo, hi):
             k = (int(krf[i]), int(kls[i]))
+            # hash-partition guarantee: every partial of a group lands in ONE partition
+            assert home.setdefault(k, p) == p, (
+                f"group {k} appears in partitions {home[k]} and {p}")
             acc = final.setdefault(k, [0.0, 0.0, 0])
             acc[0] += sq[i]
             acc[1] += sp[i]
             acc[2] += int(cn[i])
-            seen_here.add(k)
-        for k in seen_here:  # hash-partition guarantee: one partition per group
-            assert final[k] is not None
+    assert off[P] == m and sum(v[2] for v in final.values()) == n  # rows conserved
 
     direct = pa.table({"rf": rf, "ls": ls, "qty": qty, "price": price}) \
         .group_by(["rf", "ls"]).aggregate([("qty", "sum"), ("price", "sum"),
