@@ -67,6 +67,24 @@ class TaskKeyC(ctypes.Structure):
     ]
 
 
+class PartitionerInfo(ctypes.Structure):
+    """dd_partitioner_info (include/dd_shuffle.h)."""
+    _fields_ = [
+        ("path", ctypes.c_int32),
+        ("wpb", ctypes.c_int32),
+        ("gmax", ctypes.c_int32),
+        ("hl", ctypes.c_int32),
+        ("rhash", ctypes.c_int32),
+        ("pid_elem", ctypes.c_int32),
+        ("k5", ctypes.c_int32),
+        ("k5_wpb", ctypes.c_int32),
+        ("k5_maxlen", ctypes.c_int32),
+        ("rpb", ctypes.c_int32),
+        ("round_rows", ctypes.c_int64),
+        ("n_launch", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -152,6 +170,8 @@ class DeviceBatch:
         self.n_rows = (len(cols[0]["offsets"]) - 1 if cols[0]["dtype"] == "utf8"
                        else len(cols[0]["data"]))
         self._bufs = []
+        self._host_refs = (None, None)
+        self._utf8_maxlen = {}  # col -> longest string uploaded at construction
         self.desc = BatchDesc()
         self.desc.n_rows = self.n_rows
         self.desc.n_cols = len(cols)
@@ -165,6 +185,7 @@ class DeviceBatch:
                 cd.data = b
                 cd.offsets = self._up(off)
                 cd.data_len = int(data.nbytes)
+                self._utf8_maxlen[i] = int(np.diff(off).max()) if len(off) > 1 else 0
             else:
                 npdt = FIXED_NP[col["dtype"]]
                 data = np.ascontiguousarray(col["data"], dtype=npdt)
@@ -187,6 +208,8 @@ class DeviceBatch:
         self.cols = view_cols
         self.n_rows = n_rows
         self._bufs = []
+        self._host_refs = (None, None)
+        self._utf8_maxlen = {}
         self.desc = BatchDesc()
         self.desc.n_rows = n_rows
         self.desc.n_cols = len(view_cols)
@@ -210,6 +233,97 @@ class DeviceBatch:
         _h2d(p, arr)
         self._bufs.append(p)
         return p.value
+
+    def _refill_plan(self, cols):
+        """Validate `cols` against this batch under the partitioner reuse contract
+        (dd_shuffle.h, above dd_partitioner_run) and return the (device pointer, host
+        array) copies a refill would make. Raises ValueError on the first mismatch;
+        touches neither the device nor the library."""
+        if len(cols) != self.desc.n_cols:
+            raise ValueError(f"refill: {len(cols)} columns, batch has {self.desc.n_cols}")
+        n = self.n_rows
+        plan = []
+        for i, col in enumerate(cols):
+            cd = self.desc.cols[i]
+            old = self.cols[i]
+            if DTYPE_CODE.get(col["dtype"]) != cd.dtype:
+                raise ValueError(f"refill: column {i} dtype {col['dtype']} differs")
+            if col["dtype"] == "utf8":
+                data = np.ascontiguousarray(col["data"], dtype=np.uint8)
+                off = np.ascontiguousarray(col["offsets"], dtype=np.int32)
+                if len(off) != n + 1:
+                    raise ValueError(f"refill: column {i} has {len(off) - 1} rows, "
+                                     f"batch has {n}")
+                if int(data.nbytes) != cd.data_len or int(off[-1]) != cd.data_len or \
+                        int(off[0]) != 0:
+                    raise ValueError(f"refill: column {i} utf8 byte total differs from "
+                                     f"{cd.data_len}")
+                lens = np.diff(off)
+                if n and int(lens.min()) < 0:
+                    raise ValueError(f"refill: column {i} offsets decrease")
+                # longest string the batch has ever held == what a partitioner created
+                # on it may have sized its LDS image from
+                longest = self._utf8_maxlen.get(i)
+                if longest is None:
+                    raise ValueError(f"refill: column {i} create-time string lengths "
+                                     "unknown (device-view batch)")
+                if n and int(lens.max()) > longest:
+                    raise ValueError(f"refill: column {i} has a string longer than "
+                                     f"{longest} bytes")
+                plan += [(cd.data, data), (cd.offsets, off)]
+            else:
+                data = np.ascontiguousarray(col["data"], dtype=FIXED_NP[col["dtype"]])
+                if len(data) != n:
+                    raise ValueError(f"refill: column {i} has {len(data)} rows, "
+                                     f"batch has {n}")
+                plan.append((cd.data, data))
+            valid = col.get("valid")
+            if (valid is not None) != bool(cd.validity):
+                raise ValueError(f"refill: column {i} validity presence differs")
+            if valid is not None:
+                valid = np.ascontiguousarray(valid, dtype=np.uint8)
+                if len(valid) != n:
+                    raise ValueError(f"refill: column {i} validity length differs")
+                plan.append((cd.validity, valid))
+            if col["dtype"] == "dict32":
+                same = "dict_offsets" in old and \
+                    np.array_equal(np.asarray(col["dict_offsets"], dtype=np.int32),
+                                   np.asarray(old["dict_offsets"], dtype=np.int32)) and \
+                    np.array_equal(np.asarray(col["dict_bytes"], dtype=np.uint8),
+                                   np.asarray(old["dict_bytes"], dtype=np.uint8))
+                if not same:
+                    raise ValueError(f"refill: column {i} dictionary differs (dict32 key "
+                                     "hashes are computed at partitioner create time)")
+                live = data if valid is None else data[valid != 0]
+                if len(live) and (int(live.min()) < 0 or int(live.max()) >= cd.dict_n):
+                    raise ValueError(f"refill: column {i} has an index outside the "
+                                     "dictionary")
+        return plan
+
+    def refill(self, cols, stream=None):
+        """Upload new host columns into the EXISTING device buffers, for re-running a
+        partitioner created on this batch (reuse contract: dd_shuffle.h). Same dtypes,
+        n_rows and validity presence; utf8: same byte total and no string longer than
+        the longest this batch started with; dict32: the same dictionary. Any mismatch
+        raises ValueError before anything is copied.
+
+        stream=None copies synchronously. With a stream the copies are queued on it
+        (dd_memcpy_h2d_async): they overlap other streams when the arrays are pinned host
+        memory, and the caller keeps `cols` alive and unchanged until the stream has
+        passed them. Ordering against the previous run (wait_phase2) is the caller's."""
+        plan = self._refill_plan(cols)
+        for dst, arr in plan:
+            if arr.nbytes == 0:
+                continue
+            if stream is None:
+                _h2d(ctypes.c_void_p(dst), arr)
+            else:
+                _check(lib().dd_memcpy_h2d_async(
+                    ctypes.c_void_p(dst), arr.ctypes.data_as(ctypes.c_void_p),
+                    ctypes.c_int64(arr.nbytes), _stream_arg(stream)))
+        # converted temporaries of this refill and the one before stay alive
+        self._host_refs = (self._host_refs[1], [arr for _, arr in plan])
+        self.cols = cols
 
     def free(self):
         for b in self._bufs:
@@ -258,6 +372,14 @@ class Partitioner:
 
     def sync(self):
         _check(lib().dd_device_sync())
+
+    def info(self):
+        """The plan dd_partitioner_create chose, as a dict of dd_partitioner_info's
+        fields (path 0 v1 / 1 staged / 2 pre, wpb, gmax, hl, rhash, pid_elem, k5, k5_wpb,
+        k5_maxlen, rpb, round_rows, n_launch). Needs no run."""
+        out = PartitionerInfo()
+        _check(lib().dd_partitioner_get_info(self.h, ctypes.byref(out)))
+        return {name: int(getattr(out, name)) for name, _ in PartitionerInfo._fields_}
 
     def has_pid_array(self):
         """Fast null-check of the device pid pointer (no download): False when the spec

@@ -86,6 +86,12 @@ extern "C" dd_status dd_memcpy_h2d(void *dst, const void *src, int64_t bytes) {
     HIP_TRY(hipMemcpy(dst, src, (size_t)bytes, hipMemcpyHostToDevice));
     return DD_OK;
 }
+extern "C" dd_status dd_memcpy_h2d_async(void *dst, const void *src, int64_t bytes,
+                                          void *stream) {
+    HIP_TRY(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice,
+                           (hipStream_t)stream));
+    return DD_OK;
+}
 extern "C" dd_status dd_memcpy_d2h(void *dst, const void *src, int64_t bytes) {
     HIP_TRY(hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDeviceToHost));
     return DD_OK;
@@ -783,6 +789,25 @@ extern "C" void dd_partitioner_destroy(dd_partitioner *p) { delete p; }
 
 extern "C" int32_t dd_partitioner_pid_elem(const dd_partitioner *p) {
     return p->ka.pid8 ? 1 : 4;
+}
+
+extern "C" dd_status dd_partitioner_get_info(const dd_partitioner *p,
+                                             dd_partitioner_info *out) {
+    if (!p || !out) return set_err(DD_ERR_INVALID, "null argument");
+    const bool tiled = p->staged || p->pre;
+    out->path = p->pre ? 2 : (p->staged ? 1 : 0);
+    out->wpb = tiled ? p->wpb : 0;
+    out->gmax = tiled ? p->gmax : 0;
+    out->hl = p->ka.hl;
+    out->rhash = p->ka.rhash;
+    out->pid_elem = p->ka.pid8 ? 1 : 4;
+    out->k5 = p->k5;
+    out->k5_wpb = p->k5 ? p->k5_wpb : 0;
+    out->k5_maxlen = (int32_t)p->k5_maxlen;
+    out->rpb = p->pre ? p->rpb : 0;
+    out->round_rows = tiled ? (int64_t)p->gmax * p->wpb * 64 : 0;
+    out->n_launch = p->pre ? p->nrounds : p->nchunks;
+    return DD_OK;
 }
 
 extern "C" const uint32_t *dd_partitioner_pids(const dd_partitioner *p) { return p->pid; }

@@ -91,7 +91,22 @@ typedef struct dd_partitioner dd_partitioner; /* opaque */
 dd_status dd_partitioner_create(const dd_batch_desc *batch, const int32_t *key_cols,
                                 int32_t n_keys, uint32_t n_partitions,
                                 dd_partitioner **out);
-/* Runs K1 (hash+count), K2 (scan), K3 (stable scatter) on `stream` (a hipStream_t, or NULL
+/* Reuse contract. A partitioner may be run any number of times; every run recomputes the
+ * whole result from the input buffers named at create time, and no workspace state
+ * carries over from the run before. Between runs the caller may overwrite IN PLACE, with
+ * n_rows unchanged, the contents of:
+ *   - fixed-width data (key or payload), bool and dict32 indices included;
+ *   - validity bytes (a column keeps having, or not having, a validity buffer);
+ *   - utf8 bytes and offsets, provided offsets[n_rows] stays equal to data_len and no
+ *     string is longer than the longest one at create time (the LDS-staged byte scatter
+ *     sizes its image from that length).
+ * The dictionary bytes and offsets of a dict32 KEY column must not change: their hashes
+ * are computed once, at create time. Pointers, dtypes, data_len and dict_n are fixed.
+ * Each overwrite must be ordered after dd_partitioner_wait_phase2 of the previous run
+ * (or a device sync), and the next run after the overwrite. Anything else is undefined
+ * and may fault the device.
+ *
+ * Runs K1 (hash+count), K2 (scan), K3 (stable scatter) on `stream` (a hipStream_t, or NULL
  * for the default stream). Asynchronous; results valid after stream sync. */
 dd_status dd_partitioner_run(dd_partitioner *p, void *stream);
 /* coarse-bucket variant: pid = (h % pid_total) / coarse_div — pid_total/coarse_div
@@ -111,6 +126,24 @@ dd_status dd_partitioner_run_phase2(dd_partitioner *p, void *stream);
 dd_status dd_partitioner_wait_phase1(dd_partitioner *p, void *stream);
 dd_status dd_partitioner_wait_phase2(dd_partitioner *p, void *stream);
 void dd_partitioner_destroy(dd_partitioner *p);
+
+/* Read-only view of the plan dd_partitioner_create chose (which scatter tier, which block
+ * shape), so tests and benchmarks can assert the tier they mean to measure instead of
+ * mirroring the gates. Needs no run. */
+typedef struct dd_partitioner_info {
+    int32_t path;      /* 0 = v1 (k_scatter), 1 = staged, 2 = pre (K3-P) */
+    int32_t wpb, gmax; /* staged/pre block shape; 0 on v1 */
+    int32_t hl;        /* 0 none, 1 k_scatter_hl, 2 k_scatter_hlg */
+    int32_t rhash;     /* 1: K3 recomputes hashes, no pid array */
+    int32_t pid_elem;  /* 4, or 1 for byte pids */
+    int32_t k5;        /* 1: LDS-staged var-byte scatter, 0: K4 gather (or no var col) */
+    int32_t k5_wpb;    /* K5 waves per block; 0 when k5 == 0 */
+    int32_t k5_maxlen; /* longest string at create time; 0 when k5 == 0 */
+    int32_t rpb;       /* pre: rounds per block; 0 otherwise */
+    int64_t round_rows; /* gmax*wpb*64 on staged/pre, else 0 */
+    int64_t n_launch;   /* nchunks (v1/staged) or nrounds (pre) */
+} dd_partitioner_info;
+dd_status dd_partitioner_get_info(const dd_partitioner *p, dd_partitioner_info *out);
 
 /* result accessors (pointers are device memory owned by the partitioner) */
 /* u32[n_rows] of per-row partition ids. NULL ONLY when the opt-in DD_RHASH=1 recompute
@@ -443,6 +476,9 @@ void dd_reducer_destroy(dd_reducer *r);
 dd_status dd_dev_alloc(int64_t bytes, void **out);
 dd_status dd_dev_free(void *p);
 dd_status dd_memcpy_h2d(void *dst, const void *src, int64_t bytes);
+/* asynchronous on `stream`; truly overlapped only when `src` is pinned host memory, and
+ * `src` must stay valid and unchanged until the stream has passed the copy */
+dd_status dd_memcpy_h2d_async(void *dst, const void *src, int64_t bytes, void *stream);
 dd_status dd_memcpy_d2h(void *dst, const void *src, int64_t bytes);
 dd_status dd_memcpy_d2d(void *dst, const void *src, int64_t bytes);
 dd_status dd_device_sync(void);

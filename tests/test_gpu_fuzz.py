@@ -82,7 +82,13 @@ def test_fuzz_parity_tuning_knobs(knob, monkeypatch):
         random_col(rng, n, "f64", 0),
         random_col(rng, n, "bool", 0.3),
     ]
-    check_against_oracle(cols, [0, 3], 32)
+    staged = {"path": 1, "wpb": int(wpb), "gmax": int(gmax)}
+    # DD_V2_VAR=0 sends a batch with a utf8 column down the v1 kernels, where wpb/gmax
+    # mean nothing: those legs pin v1 on this shape and run the knobs on the same batch
+    # without its utf8 column, which is staged whatever DD_V2_VAR says
+    check_against_oracle(cols, [0, 3], 32, expect=staged if var == "1" else {"path": 0})
+    if var == "0":
+        check_against_oracle([cols[0], cols[2], cols[3]], [0, 2], 32, expect=staged)
 
 def test_rhash_ab(monkeypatch):
     """The register-recompute spec path (rhash: no pid array; opt-in DD_RHASH=1 — a
@@ -95,9 +101,14 @@ def test_rhash_ab(monkeypatch):
             random_col(rng, n, "f64", 0), random_col(rng, n, "i32", 0)]
     for keys, nparts in [([0], 128), ([1, 0], 100), ([3, 1], 777)]:
         monkeypatch.setenv("DD_RHASH", "1")
-        check_against_oracle(cols, keys, nparts)
+        check_against_oracle(cols, keys, nparts, expect={"rhash": 1, "path": 1})
         monkeypatch.delenv("DD_RHASH")
-        check_against_oracle(cols, keys, nparts)
+        check_against_oracle(cols, keys, nparts, expect={"rhash": 0, "path": 1})
+
+HL = {"path": 1, "hl": 1, "gmax": 4, "wpb": 16, "rhash": 0}  # k_scatter_hl
+HLG = {"path": 1, "hl": 2, "wpb": 16, "rhash": 0}            # k_scatter_hlg
+SPEC = {"path": 1, "hl": 0, "wpb": 16, "rhash": 0}           # k_scatter_staged, spec form
+
 
 def test_hl_ab(monkeypatch):
     """Hidden-load scatter (default for its gated shape: inline-asm preload +
@@ -111,16 +122,16 @@ def test_hl_ab(monkeypatch):
         for keys, nparts in [([0], 128), ([3, 0], 100)]:
             monkeypatch.setenv("DD_K3_PRE", "0")  # force the HL tier (pre outranks it)
             monkeypatch.delenv("DD_K3_HL", raising=False)  # default-within-tier: HL
-            check_against_oracle(cols, keys, nparts)
+            check_against_oracle(cols, keys, nparts, expect=HL)
             monkeypatch.setenv("DD_K3_HL", "0")  # plain spec path
-            check_against_oracle(cols, keys, nparts)
+            check_against_oracle(cols, keys, nparts, expect=SPEC)
     n = 123_457
     monkeypatch.setenv("DD_K3_PRE", "0")
     cols = [random_col(rng, n, "i32", 0), random_col(rng, n, "i64", 0),
             random_col(rng, n, "f32", 0), random_col(rng, n, "f64", 0)]
     monkeypatch.delenv("DD_K3_HL", raising=False)
-    check_against_oracle(cols, [0, 1], 128)
-    check_against_oracle(cols, [2, 3], 100)
+    check_against_oracle(cols, [0, 1], 128, expect=HL)
+    check_against_oracle(cols, [2, 3], 100, expect=HL)
 
 def test_hlg_ab(monkeypatch):
     """Generalized hidden-load scatter (k_scatter_hlg, whitelisted 5-col multikey and
@@ -139,9 +150,16 @@ def test_hlg_ab(monkeypatch):
                                    (q1, [0, 1], 128), (q1, [0, 1], 7)]:
             monkeypatch.setenv("DD_K3_PRE", "0")  # force the hlg tier (pre outranks it)
             monkeypatch.delenv("DD_K3_HL", raising=False)  # default-within-tier: hlg
-            check_against_oracle(cols, keys, nparts)
+            check_against_oracle(cols, keys, nparts, expect=HLG)
             monkeypatch.setenv("DD_K3_HL", "0")
-            check_against_oracle(cols, keys, nparts)
+            check_against_oracle(cols, keys, nparts, expect=SPEC)
+
+
+def pre(nparts):
+    """k_scatter_pre's tier for the 4- and 5-column shapes: G4 up to P = 256 with byte
+    pids, G2 with u32 pids up to 512."""
+    return {"path": 2, "wpb": 16, "gmax": 4 if nparts <= 256 else 2,
+            "pid_elem": 1 if nparts <= 256 else 4, "hl": 0, "rhash": 0}
 
 
 def test_pre_ab(monkeypatch):
@@ -157,25 +175,25 @@ def test_pre_ab(monkeypatch):
         for keys, nparts in [([0], 128), ([0], 100), ([0], 1), ([3, 0], 256),
                              ([0], 200), ([0], 512), ([0], 300)]:
             monkeypatch.delenv("DD_K3_PRE", raising=False)  # default: pre
-            check_against_oracle(cols, keys, nparts)
+            check_against_oracle(cols, keys, nparts, expect=pre(nparts))
             monkeypatch.setenv("DD_K3_PRE", "0")
-            check_against_oracle(cols, keys, nparts)
+            check_against_oracle(cols, keys, nparts, expect={"path": 1, "wpb": 16})
     # mixed 4/8 shapes (tier 1) + multikey + q1 shapes through the pre path
     n = 123_457
     monkeypatch.delenv("DD_K3_PRE", raising=False)
     mixed = [random_col(rng, n, "i32", 0), random_col(rng, n, "i64", 0),
              random_col(rng, n, "f32", 0), random_col(rng, n, "f64", 0)]
-    check_against_oracle(mixed, [0, 1], 128)
-    check_against_oracle(mixed, [2, 3], 97)
+    check_against_oracle(mixed, [0, 1], 128, expect=pre(128))
+    check_against_oracle(mixed, [2, 3], 97, expect=pre(97))
     mk = [random_col(rng, n, "i64", 0), random_col(rng, n, "f64", 0),
           random_col(rng, n, "f64", 0), random_col(rng, n, "i32", 0),
           random_col(rng, n, "i32", 0)]
-    check_against_oracle(mk, [0, 4], 128)
-    check_against_oracle(mk, [0, 4], 512)  # multikey P<=512 tier (G2, NBG8)
-    check_against_oracle(mk, [0, 4], 300)
+    check_against_oracle(mk, [0, 4], 128, expect=pre(128))
+    check_against_oracle(mk, [0, 4], 512, expect=pre(512))  # multikey P<=512 tier (G2, NBG8)
+    check_against_oracle(mk, [0, 4], 300, expect=pre(300))
     q1 = [random_col(rng, n, "u8", 0), random_col(rng, n, "bool", 0),
           random_col(rng, n, "f64", 0), random_col(rng, n, "f64", 0),
           random_col(rng, n, "f64", 0), random_col(rng, n, "f64", 0),
           random_col(rng, n, "i32", 0)]
-    check_against_oracle(q1, [0, 1], 128)
-    check_against_oracle(q1, [0, 1], 7)
+    check_against_oracle(q1, [0, 1], 128, expect={"path": 2, "gmax": 2, "pid_elem": 1})
+    check_against_oracle(q1, [0, 1], 7, expect={"path": 2, "gmax": 2, "pid_elem": 1})

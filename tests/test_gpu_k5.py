@@ -33,8 +33,11 @@ def test_k5_threshold_boundary(maxlen, k5, monkeypatch):
         utf8_col(rng, n, 8, maxlen),
         {"dtype": "i32", "data": rng.integers(0, 99, n).astype(np.int32), "valid": None},
     ]
-    check_against_oracle(cols, [0], 64)
-    check_against_oracle(cols, [0], 100)
+    # K5 only inside its gate and with DD_K5 on; everywhere else the K4 gather
+    on = k5 == "1" and maxlen <= 128
+    expect = {"path": 1, "k5": 1, "k5_maxlen": maxlen} if on else {"path": 1, "k5": 0}
+    check_against_oracle(cols, [0], 64, expect=expect)
+    check_against_oracle(cols, [0], 100, expect=expect)
 
 
 def test_k5_edge_shapes(monkeypatch):

@@ -23,44 +23,63 @@ gen_golden = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(gen_golden)
 
 
-def run_gpu(cols, key_idx, nparts):
+def compare_to_oracle(part, cols, key_idx, nparts, ref=None):
+    """Compare everything a run partitioner exposes with the CPU oracle's repartition of
+    `cols`: pids (when the path keeps a pid array), row offsets, every column's data,
+    validity, utf8 lengths, bytes and byte offsets. `ref` passes in an oracle result
+    computed earlier for the same arguments."""
+    if ref is None:
+        ref = oracle.repartition(cols, key_idx, nparts)
+    n = part.batch.n_rows
+    pd = part.pids()  # None when the spec path recomputes hashes in-kernel
+    if n and pd is not None:
+        assert (pd == ref["pid"]).all(), "partition ids differ"
+    assert (part.row_offsets() == ref["part_offsets"]).all(), "row offsets differ"
+    for i, col in enumerate(cols):
+        got = part.col_out(i)
+        exp = ref["cols"][i]
+        if col["dtype"] == "utf8":
+            assert (got["lengths"] == exp["lengths"]).all(), f"col {i} lengths differ"
+            assert got["data"].tobytes() == exp["data"].tobytes(), f"col {i} bytes differ"
+            # byte offsets = prefix of lengths at partition boundaries
+            boff = part.byte_offsets(i)
+            lens64 = exp["lengths"].astype(np.int64)
+            pref = np.zeros(n + 1, dtype=np.int64)
+            if n:
+                pref[1:] = np.cumsum(lens64)
+            expected_boff = pref[ref["part_offsets"]]
+            assert (boff == expected_boff).all(), f"col {i} byte offsets differ"
+        elif col["dtype"] in ("f32", "f64"):
+            assert np.array_equal(got["data"], exp["data"], equal_nan=True), \
+                f"col {i} data differ"
+        else:
+            assert (got["data"] == exp["data"]).all(), f"col {i} data differ"
+        if col.get("valid") is not None:
+            assert (got["valid"] == exp["valid"]).all(), f"col {i} validity differs"
+
+
+def assert_info(part, expect):
+    """Assert the plan the partitioner chose (Partitioner.info()). `expect` maps a field
+    to its required value, or to a predicate over the value."""
+    info = part.info()
+    for name, want in (expect or {}).items():
+        got = info[name]
+        good = want(got) if callable(want) else got == want
+        assert good, f"info()[{name!r}] = {got}, not the tier this test names: {info}"
+    return info
+
+
+def check_against_oracle(cols, key_idx, nparts, expect=None):
+    """One create / run / compare / destroy. `expect` (see assert_info) pins the scatter
+    tier the case is meant to exercise, checked before the run."""
+    ref = oracle.repartition(cols, key_idx, nparts)
     batch = api.DeviceBatch(cols)
     part = api.Partitioner(batch, key_idx, nparts)
-    part.run()
-    part.sync()
-    return batch, part
-
-
-def check_against_oracle(cols, key_idx, nparts):
-    ref = oracle.repartition(cols, key_idx, nparts)
-    batch, part = run_gpu(cols, key_idx, nparts)
     try:
-        n = batch.n_rows
-        pd = part.pids()  # None when the spec path recomputes hashes in-kernel
-        if n and pd is not None:
-            assert (pd == ref["pid"]).all(), "partition ids differ"
-        assert (part.row_offsets() == ref["part_offsets"]).all(), "row offsets differ"
-        for i, col in enumerate(cols):
-            got = part.col_out(i)
-            exp = ref["cols"][i]
-            if col["dtype"] == "utf8":
-                assert (got["lengths"] == exp["lengths"]).all(), f"col {i} lengths differ"
-                assert got["data"].tobytes() == exp["data"].tobytes(), f"col {i} bytes differ"
-                # byte offsets = prefix of lengths at partition boundaries
-                boff = part.byte_offsets(i)
-                lens64 = exp["lengths"].astype(np.int64)
-                pref = np.zeros(n + 1, dtype=np.int64)
-                if n:
-                    pref[1:] = np.cumsum(lens64)
-                expected_boff = pref[ref["part_offsets"]]
-                assert (boff == expected_boff).all(), f"col {i} byte offsets differ"
-            elif col["dtype"] in ("f32", "f64"):
-                assert np.array_equal(got["data"], exp["data"], equal_nan=True), \
-                    f"col {i} data differ"
-            else:
-                assert (got["data"] == exp["data"]).all(), f"col {i} data differ"
-            if col.get("valid") is not None:
-                assert (got["valid"] == exp["valid"]).all(), f"col {i} validity differs"
+        assert_info(part, expect)
+        part.run()
+        part.sync()
+        compare_to_oracle(part, cols, key_idx, nparts, ref=ref)
     finally:
         part.destroy()
         batch.free()
@@ -211,4 +230,5 @@ def test_gpu_staged_var_two_utf8_with_nulls(staged_var, monkeypatch):
         utf8(8, 0.0),
         {"dtype": "f64", "data": rng.normal(size=n), "valid": None},
     ]
-    check_against_oracle(cols, [0], 64)
+    check_against_oracle(cols, [0], 64, expect={"path": 0} if staged_var == "0"
+                         else {"path": 1, "k5": 0})
