@@ -108,6 +108,8 @@ def lib():
         L.dd_exchanged_col_validity.restype = ctypes.c_void_p
         L.dd_exchanged_col_lengths.restype = ctypes.c_void_p
         L.dd_exchanged_total_rows.restype = ctypes.c_int64
+        L.dd_pre_xcd_block_map.restype = None
+        L.dd_pre_xcd_block_map.argtypes = [ctypes.c_int64, ctypes.c_void_p]
         L.dd_bcast_n_rows.restype = ctypes.c_int64
         L.dd_bcast_n_cols.restype = ctypes.c_int32
         L.dd_bcast_col_data.restype = ctypes.c_void_p
@@ -380,6 +382,11 @@ class Partitioner:
         out = PartitionerInfo()
         _check(lib().dd_partitioner_get_info(self.h, ctypes.byref(out)))
         return {name: int(getattr(out, name)) for name, _ in PartitionerInfo._fields_}
+
+    def pre_layout(self):
+        """0 not the pre path, 1 segment-granular layout precompute, 2 round-granular
+        (dd_partitioner_pre_layout; DD_PRE_LAYOUT=seg|round at create time)."""
+        return int(lib().dd_partitioner_pre_layout(self.h))
 
     def has_pid_array(self):
         """Fast null-check of the device pid pointer (no download): False when the spec

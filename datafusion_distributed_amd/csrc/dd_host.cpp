@@ -141,6 +141,9 @@ struct dd_partitioner {
     int rpb = 1;                       /* pre: rounds per block */
     int pre_nranges = 0;               /* pre: scan ranges (segment-granular counts) */
     uint32_t sP2 = 0;                  /* pre: imgb row stride (u16, even) */
+    int pre_layout = 0; /* 0 not pre, 1 seg (k_hash_count_seg), 2 round (k_hash_count_round) */
+    int pre_xcd = 0;    /* DD_PRE_XCD=1: k_scatter_pre walks rounds in XCD-contiguous order */
+    int round_nr1 = 0, round_nr2 = 0; /* round layout: scan ranges (nr2 == 0: one level) */
 
     /* device buffers (owned) */
     uint32_t *pid = nullptr;
@@ -152,8 +155,12 @@ struct dd_partitioner {
     uint64_t *part_boffsets = nullptr;   /* [nvar][P+1] */
     uint16_t *imgb = nullptr;            /* pre: [nrounds][sP2] round image bases (roff) */
     uint32_t *partials2 = nullptr;       /* pre: second-level scan partials [64][P] */
-    uint16_t *counts16 = nullptr;        /* pre: [nseg][P] u16 segment counts */
-    uint32_t *gbase = nullptr;           /* pre: [nseg][P] u32 global slot bases */
+    uint16_t *counts16 = nullptr;        /* pre seg: [nseg][P] u16 segment counts;
+                                            pre round: segoff [nseg][sP2] u16 */
+    uint32_t *gbase = nullptr;           /* pre seg: [nseg][P] u32 global slot bases */
+    uint32_t *roundcnt = nullptr;        /* pre round: [nrounds][sP2] rows per round */
+    uint32_t *rbase = nullptr;           /* pre round: [nrounds][sP2] global slot bases */
+    uint32_t *totals = nullptr;          /* pre round: [sP2] rows per partition */
     uint32_t *src_row = nullptr;         /* staged-var: permutation out[slot] = input row */
     uint32_t *k4w_meta = nullptr;        /* staged-var: window hist/base (k4_copy_ord) */
     uint32_t *k4w_order = nullptr;       /* staged-var: window-bucketed group order */
@@ -193,6 +200,9 @@ struct dd_partitioner {
         (void)hipFree(k4w_order);
         (void)hipFree(counts16);
         (void)hipFree(gbase);
+        (void)hipFree(roundcnt);
+        (void)hipFree(rbase);
+        (void)hipFree(totals);
         (void)hipFree(k5_bcounts);
         (void)hipFree(k5_gbase);
         (void)hipFree(k5_partials);
@@ -445,6 +455,34 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
                     if (nr > 16384) nr = 16384;
                     p->pre_nranges = (int)nr;
                 }
+                /* layout precompute granularity: per round unless
+                 * DD_PRE_LAYOUT=seg */
+                p->pre_layout = 2;
+                if (const char *e = getenv("DD_PRE_LAYOUT")) {
+                    if (strcmp(e, "seg") == 0) p->pre_layout = 1;
+                    else if (strcmp(e, "round") != 0)
+                        return fail(DD_ERR_INVALID, "DD_PRE_LAYOUT must be seg or round");
+                }
+                /* XCD-contiguous round order in K3: default only where it measured a win
+                 * on the round layout — the 4-column shapes at P <= 128 (headline,
+                 * dictkey) and at 257..512. It LOSES on the 5-column multikey tier and
+                 * ties within noise on q1 and at 129..256.
+                 * DD_PRE_XCD=0/1 overrides on any tier. */
+                p->pre_xcd = p->pre_layout == 2 && batch->n_cols == 4 &&
+                             (n_partitions <= 128 || n_partitions > 256);
+                if (const char *e = getenv("DD_PRE_XCD")) p->pre_xcd = atoi(e) == 1;
+                /* round-granular scan: a thread walks <= span = 64 rounds; past 16*span
+                 * ranges (> 65 k rounds) the range partials get a second level of
+                 * span-range groups. DD_PRE_SCAN_SPAN (1..64) shrinks span so a small
+                 * batch reaches the two-level form (tests). */
+                int64_t span = 64;
+                if (const char *e = getenv("DD_PRE_SCAN_SPAN")) {
+                    int v = atoi(e);
+                    if (v >= 1 && v <= 64) span = v;
+                }
+                p->round_nr1 = (int)((p->nrounds + span - 1) / span);
+                p->round_nr2 =
+                    p->round_nr1 > 16 * span ? (int)((p->round_nr1 + span - 1) / span) : 0;
                 p->nchunks = p->nseg_pad;       /* counts rows (scan granularity) */
                 p->chunk_rows = (int64_t)pgmax * 64; /* = SEG (K1seg rows per wave) */
                 p->lds_k1 = (size_t)WAVES_PER_BLOCK_H * n_partitions * 4;
@@ -521,9 +559,18 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
                         : halloc((void **)&p->pid, (size_t)n * (ka.pid8 ? 1 : 4))) &&
               halloc((void **)&p->counts, p->pre ? 4 : (size_t)nchunks * P * 4) &&
               halloc((void **)&p->partials,
-                     (size_t)(p->pre ? p->pre_nranges : DD_SCAN_RANGES) * P * 4) &&
+                     p->pre_layout == 2
+                         ? (size_t)p->round_nr1 * p->sP2 * 4
+                         : (size_t)(p->pre ? p->pre_nranges : DD_SCAN_RANGES) * P * 4) &&
               halloc((void **)&p->part_offsets, (size_t)(P + 1) * 8);
-    if (ok && p->pre)
+    if (ok && p->pre_layout == 2) /* round-layout tables carry sP2 columns */
+        ok = halloc((void **)&p->imgb, (size_t)p->nrounds * p->sP2 * 2) &&
+             halloc((void **)&p->partials2, (size_t)(p->round_nr2 + 1) * p->sP2 * 4) &&
+             halloc((void **)&p->counts16, (size_t)p->nseg_pad * p->sP2 * 2) &&
+             halloc((void **)&p->roundcnt, (size_t)p->nrounds * p->sP2 * 4) &&
+             halloc((void **)&p->rbase, (size_t)p->nrounds * p->sP2 * 4) &&
+             halloc((void **)&p->totals, (size_t)p->sP2 * 4);
+    else if (ok && p->pre)
         ok = halloc((void **)&p->imgb, (size_t)p->nrounds * p->sP2 * 2) &&
              halloc((void **)&p->partials2, (size_t)64 * P * 4) &&
              halloc((void **)&p->counts16, (size_t)p->nseg_pad * P * 2) &&
@@ -679,7 +726,11 @@ extern "C" dd_status dd_partitioner_run_phase1(dd_partitioner *p, void *stream) 
     if (!p) return set_err(DD_ERR_INVALID, "null partitioner");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipEventRecord(p->ev[0], s));
-    if (p->pre) {
+    if (p->pre_layout == 2) {
+        HIP_TRY(dd_launch_hash_count_round(&p->ka, p->nrounds, p->chunk_rows, p->wpb,
+                                           p->nparts, p->sP2, p->pid, p->counts16,
+                                           p->roundcnt, p->imgb, s));
+    } else if (p->pre) {
         HIP_TRY(hipMemsetAsync(p->partials, 0, (size_t)p->pre_nranges * p->nparts * 4, s));
         HIP_TRY(dd_launch_hash_count_seg(&p->ka, p->nseg_pad, p->chunk_rows, p->nparts,
                                          p->nbits, p->pid, p->counts16, p->partials,
@@ -692,7 +743,12 @@ extern "C" dd_status dd_partitioner_run_phase1(dd_partitioner *p, void *stream) 
                                      p->pid, p->counts, p->bcounts, p->lds_k1, s));
     }
     HIP_TRY(hipEventRecord(p->ev[1], s));
-    if (p->pre) {
+    if (p->pre_layout == 2) {
+        HIP_TRY(dd_launch_scan_round(p->roundcnt, p->nrounds, p->nparts, p->sP2,
+                                     p->round_nr1, p->round_nr2, p->partials,
+                                     p->partials2, p->totals, p->part_offsets, p->rbase,
+                                     s));
+    } else if (p->pre) {
         HIP_TRY(dd_launch_scan_deep(p->counts16, p->nchunks, p->nparts, p->pre_nranges,
                                     64, p->partials, p->partials2, p->part_offsets,
                                     p->gbase, s));
@@ -700,7 +756,7 @@ extern "C" dd_status dd_partitioner_run_phase1(dd_partitioner *p, void *stream) 
         HIP_TRY(dd_launch_scan(p->counts, p->nchunks, p->nparts, DD_SCAN_RANGES,
                                p->partials, p->part_offsets, 0, s));
     }
-    if (p->pre) {
+    if (p->pre_layout == 1) {
         HIP_TRY(dd_launch_round_layout(p->gbase, p->part_offsets, p->nrounds, p->wpb,
                                        p->nparts, p->sP2, p->imgb, s));
     }
@@ -738,6 +794,7 @@ extern "C" dd_status dd_partitioner_run_phase2(dd_partitioner *p, void *stream) 
         const int64_t nblocks = (p->nrounds + p->rpb - 1) / p->rpb;
         HIP_TRY(dd_launch_scatter_pre(&p->ka, nblocks, p->nrounds, p->rpb, p->nparts,
                                       p->nbits, p->pid, p->gbase, p->imgb, p->sP2,
+                                      p->counts16, p->rbase, p->pre_layout, p->pre_xcd,
                                       p->gmax, p->wpb, p->lds_k3, s));
     } else if (p->staged) {
         HIP_TRY(dd_launch_scatter_staged(&p->ka, p->nchunks, p->chunk_rows, p->nparts,
@@ -789,6 +846,14 @@ extern "C" void dd_partitioner_destroy(dd_partitioner *p) { delete p; }
 
 extern "C" int32_t dd_partitioner_pid_elem(const dd_partitioner *p) {
     return p->ka.pid8 ? 1 : 4;
+}
+
+extern "C" int32_t dd_partitioner_pre_layout(const dd_partitioner *p) {
+    return p ? p->pre_layout : 0;
+}
+
+extern "C" void dd_pre_xcd_block_map(int64_t nblocks, int64_t *out) {
+    for (int64_t b = 0; b < nblocks; b++) out[b] = dd_xcd_block_map(b, nblocks);
 }
 
 extern "C" dd_status dd_partitioner_get_info(const dd_partitioner *p,

@@ -86,6 +86,18 @@ struct dd_gc_tile {
 
 #include "dd_shuffle.h" /* dd_status for dd_set_error */
 
+/* DD_PRE_XCD=1 block map of k_scatter_pre. Workgroups are dealt round-robin over
+ * DD_NXCD dies with private L2s, so hardware blocks b, b+8, b+16, ... share one; this
+ * hands those the contiguous logical run [start(x), start(x) + count(x)), x = b % 8,
+ * count(x) = floor(nblocks/8) + (x < nblocks % 8). A bijection onto [0, nblocks) for
+ * every nblocks (tests/test_xcd_map.py). */
+#define DD_NXCD 8
+__host__ __device__ inline int64_t dd_xcd_block_map(int64_t b, int64_t nblocks) {
+    const int64_t q = nblocks / DD_NXCD, rem = nblocks % DD_NXCD;
+    const int64_t x = b % DD_NXCD;
+    return x * q + (x < rem ? x : rem) + b / DD_NXCD;
+}
+
 extern "C" {
 hipError_t dd_launch_gc_mark(const dd_gc_tile *tiles, int64_t n_tiles, const int32_t *idx,
                              const uint8_t *valid, uint32_t dict_n, uint32_t nw, int lds,
@@ -142,8 +154,18 @@ hipError_t dd_launch_round_layout(const uint32_t *counts, const uint64_t *part_o
 hipError_t dd_launch_scatter_pre(const dd_kargs *a, int64_t nblocks, int64_t nrounds,
                                  int rpb, uint32_t nparts, int nbits,
                                  const uint32_t *pid_in, const uint32_t *gbase,
-                                 const uint16_t *imgb, uint32_t sP2, int gmax, int wpb,
-                                 size_t lds_bytes, hipStream_t s);
+                                 const uint16_t *imgb, uint32_t sP2, const uint16_t *segoff,
+                                 const uint32_t *rbase, int layout, int xcd, int gmax,
+                                 int wpb, size_t lds_bytes, hipStream_t s);
+hipError_t dd_launch_hash_count_round(const dd_kargs *a, int64_t nrounds, int64_t seg_rows,
+                                      int wpb, uint32_t nparts, uint32_t sP2,
+                                      uint32_t *pid_out, uint16_t *segoff,
+                                      uint32_t *roundcnt, uint16_t *rofftab,
+                                      hipStream_t s);
+hipError_t dd_launch_scan_round(const uint32_t *roundcnt, int64_t nrounds, uint32_t nparts,
+                                uint32_t sP2, int nr1, int nr2, uint32_t *partials,
+                                uint32_t *partials2, uint32_t *totals,
+                                uint64_t *part_offsets, uint32_t *rbase, hipStream_t s);
 hipError_t dd_launch_hash_count_tile(const dd_kargs *a, int64_t nblocks, int64_t tile_rows,
                                      uint32_t nparts, int nbits, uint32_t *pid_out,
                                      uint32_t *counts, size_t lds_bytes, hipStream_t s);

@@ -164,6 +164,98 @@ __global__ void k_scan_rewrite(uint32_t *counts, int64_t nchunks, uint32_t npart
     }
 }
 
+/* K2a (round layout): k_scan_partial with the loads of a range batched 8 deep — the
+ * plain loop measured 28 us for 1.9 M entries, latency-bound at one load in flight */
+__global__ void k_scan_partial_round(const uint32_t *__restrict__ counts, int64_t nchunks,
+                                     uint32_t nparts, int nranges,
+                                     uint32_t *__restrict__ partials) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = (int64_t)nranges * nparts;
+    if (tid >= total) return;
+    const int r = (int)(tid / nparts);
+    const uint32_t p = (uint32_t)(tid % nparts);
+    const int64_t c0 = nchunks * r / nranges, c1 = nchunks * (r + 1) / nranges;
+    uint32_t s = 0;
+    int64_t c = c0;
+    for (; c + 8 <= c1; c += 8) {
+        uint32_t v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = counts[(c + u) * nparts + p];
+#pragma unroll
+        for (int u = 0; u < 8; u++) s += v[u];
+    }
+    for (; c < c1; c++) s += counts[c * nparts + p];
+    partials[(size_t)r * nparts + p] = s;
+}
+
+/* K2b, parallel over ranges (round layout): one WAVE per partition walks its column of
+ * range partials 64 ranges at a time (shfl scan + carry) and rewrites it exclusive in
+ * place; the column total goes to totals[p]. k_scan_combine's one-thread-per-partition
+ * walk pays one dependent load/store round trip per range. */
+__global__ __launch_bounds__(BLOCK_THREADS) void k_scan_combine_wave(
+    uint32_t *partials, int nranges, uint32_t nparts, uint32_t *totals) {
+    const int lane = threadIdx.x % WAVE;
+    const uint32_t p = blockIdx.x * WAVES_PER_BLOCK + threadIdx.x / WAVE;
+    if (p >= nparts) return; /* whole wave */
+    uint32_t carry = 0;
+    for (int r0 = 0; r0 < nranges; r0 += WAVE) {
+        const int r = r0 + lane;
+        const uint32_t c = (r < nranges) ? partials[(size_t)r * nparts + p] : 0;
+        uint32_t v = c;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            uint32_t u = (uint32_t)__shfl_up((int)v, d);
+            if (lane >= d) v += u;
+        }
+        if (r < nranges) partials[(size_t)r * nparts + p] = carry + v - c;
+        carry += (uint32_t)__shfl((int)v, WAVE - 1);
+    }
+    if (lane == 0) totals[p] = carry;
+}
+
+/* one wave: part_offsets[P+1] (u64) = exclusive scan of the per-partition totals */
+__global__ __launch_bounds__(WAVE) void k_part_offsets(const uint32_t *totals,
+                                                       uint32_t nparts,
+                                                       uint64_t *part_offsets) {
+    const int lane = threadIdx.x;
+    unsigned long long carry = 0;
+    for (uint32_t p0 = 0; p0 < nparts; p0 += WAVE) {
+        const uint32_t p = p0 + lane;
+        const unsigned long long c = (p < nparts) ? totals[p] : 0;
+        unsigned long long v = c;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            unsigned long long u = __shfl_up(v, d);
+            if (lane >= d) v += u;
+        }
+        if (p < nparts) part_offsets[p] = carry + v - c;
+        carry += __shfl(v, WAVE - 1);
+    }
+    if (lane == 0) part_offsets[nparts] = carry;
+}
+
+/* K2c (round layout): roundcnt[nrounds][P] -> rbase[r][p] = first GLOBAL output slot of
+ * round r's rows for partition p (range base + part_offsets fold). Out of place, so the
+ * loads of a range do not wait on its stores. */
+__global__ void k_scan_rewrite_rbase(const uint32_t *__restrict__ roundcnt, int64_t nrounds,
+                                     uint32_t nparts, int nranges,
+                                     const uint32_t *__restrict__ partials,
+                                     const uint64_t *__restrict__ part_offsets,
+                                     uint32_t *__restrict__ rbase) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = (int64_t)nranges * nparts;
+    if (tid >= total) return;
+    const int r = (int)(tid / nparts);
+    const uint32_t p = (uint32_t)(tid % nparts);
+    const int64_t c0 = nrounds * r / nranges, c1 = nrounds * (r + 1) / nranges;
+    uint32_t run = partials[(size_t)r * nparts + p] + (uint32_t)part_offsets[p];
+#pragma unroll 8
+    for (int64_t c = c0; c < c1; c++) {
+        rbase[c * nparts + p] = run;
+        run += roundcnt[c * nparts + p];
+    }
+}
+
 /* ---------------- K3: stable scatter ---------------- */
 
 __global__ __launch_bounds__(BLOCK_THREADS) void k_scatter(
@@ -1215,13 +1307,26 @@ __global__ __launch_bounds__(16 * WAVE) void k_scatter_hlg(
  * then the base rows are written to LDS and rank runs before the round barrier.
  * NBG/NBI are compile-time dword counts for the gbase/roff row loads (host gates P to
  * the instantiated tier); roff rows are padded to even u16 (sP2) so dword loads stay
- * aligned. Parity: bit-exact vs the oracle (tests/test_gpu_fuzz.py::test_pre_ab). */
+ * aligned. Parity: bit-exact vs the oracle (tests/test_gpu_fuzz.py::test_pre_ab).
+ *
+ * RL = true (round layout, DD_PRE_LAYOUT=round, the default): the layout comes from
+ * k_hash_count_round + the round-granular scan instead. Per round each wave hidden-loads
+ * its segoff row (u16), the round's rbase row (u32) and roff row (u16), all at
+ * p = lane + k*64 (NB = 3*NBG loads, clamped redundant loads past P, same single counted
+ * wait), and write_base_rows stores wave-private gb[p] = rbase + segoff and
+ * rf[p] = roff + segoff, so
+ *   img  = rf[pid] + rank,   gdst = gb[pid] + rank
+ * with no cross-wave gb0 read; LDS carve and footprint are the seg layout's.
+ * xcd != 0 (DD_PRE_XCD): hardware block -> logical block through dd_xcd_block_map.
+ * Parity of both layouts, every tier and knob: tests/test_gpu_round_layout.py. */
 
-template <int G, int W, int NBG, int NBI, int... Es>
+template <bool RL, int G, int W, int NBG, int NBI, int... Es>
 __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
     dd_kargs a, int64_t nrounds, int rpb, uint32_t nparts, int nbits,
     const uint32_t *pid_in, const uint32_t *gbase /* [nseg][P] global slot bases */,
-    const uint16_t *rofftab /* [nrounds][sP2] round image bases */, uint32_t sP2) {
+    const uint16_t *rofftab /* [nrounds][sP2] round image bases */, uint32_t sP2,
+    const uint16_t *segoff /* RL: [nseg][sP2] */, const uint32_t *rbase /* RL: [nrounds][sP2] */,
+    int xcd) {
     constexpr int WPB = W, GMAX = G;
     constexpr int BT = WPB * WAVE;
     constexpr int R = GMAX * BT;
@@ -1229,7 +1334,7 @@ __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
     constexpr int NC = sizeof...(Es);
     constexpr int EL[NC] = {Es...};
     constexpr int L = GMAX * NC;
-    constexpr int NB = NBG + NBI;
+    constexpr int NB = RL ? 3 * NBG : NBG + NBI;
     static_assert(2 * L + NB <= 63, "vmcnt immediate is 6 bits");
     struct slots {
         int idx[NC];
@@ -1269,7 +1374,9 @@ __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
     uint16_t *ms = ms_all + (size_t)wid * nparts;
     const uint64_t lt = ((uint64_t)1 << lane) - 1;
 
-    const int64_t r0 = (int64_t)blockIdx.x * rpb;
+    /* DD_PRE_XCD=1: blocks sharing an L2 (equal blockIdx.x mod 8) walk consecutive rounds */
+    const int64_t lb = xcd ? dd_xcd_block_map(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+    const int64_t r0 = lb * rpb;
     const int64_t r1 = (r0 + rpb < nrounds) ? r0 + rpb : nrounds;
     if (r0 >= nrounds || a.n_rows == 0) return;
 
@@ -1277,7 +1384,8 @@ __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
     bool actr[GMAX];
     uint64_t big[S.n8 > 0 ? S.n8 : 1][GMAX];
     uint32_t sml[S.n4 > 0 ? S.n4 : 1][GMAX];
-    uint32_t baser[NB]; /* NBG gbase dwords then NBI roff dwords */
+    uint32_t baser[NB]; /* NBG gbase dwords then NBI roff dwords; RL: NBG segoff u16,
+                           NBG rbase u32, NBG roff u16, all at p = lane + k*64 */
 
     const uint32_t ndw = (nparts + 1) / 2; /* roff row dwords */
 
@@ -1326,6 +1434,31 @@ __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
         /* base rows (wave-private): gbase u32[P] for MY segment, then the round's roff
          * u16[sP2] as dwords (same row for all 16 waves; the table is ~4 KB/round and
          * L2-hot, so the duplicate loads are free) */
+        if constexpr (RL) {
+            /* round layout: my segment's segoff row + the round's rbase and roff rows
+             * (the last two are the same for every wave and L2-hot) */
+            const uint16_t *srow = segoff + (size_t)seg * sP2;
+            const uint32_t *brow = rbase + (size_t)r * sP2;
+            const uint16_t *irow = rofftab + (size_t)r * sP2;
+            uint32_t idxk[NBG];
+#pragma unroll
+            for (int k = 0; k < NBG; k++) {
+                idxk[k] = (uint32_t)lane + k * WAVE;
+                if (idxk[k] >= nparts) idxk[k] = nparts - 1; /* redundant re-load */
+            }
+#pragma unroll
+            for (int k = 0; k < NBG; k++)
+                asm volatile("global_load_ushort %0, %1, off"
+                             : "=v"(baser[k])
+                             : "v"(srow + idxk[k]));
+#pragma unroll
+            for (int k = 0; k < NBG; k++) HL_LD32(baser[NBG + k], brow + idxk[k]);
+#pragma unroll
+            for (int k = 0; k < NBG; k++)
+                asm volatile("global_load_ushort %0, %1, off"
+                             : "=v"(baser[2 * NBG + k])
+                             : "v"(irow + idxk[k]));
+        } else {
         const uint32_t *grow = gbase + (size_t)seg * nparts;
 #pragma unroll
         for (int k = 0; k < NBG; k++) {
@@ -1339,6 +1472,7 @@ __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
             uint32_t idx = (uint32_t)lane + k * WAVE;
             if (idx >= ndw) idx = ndw - 1;
             HL_LD32(baser[NBG + k], irow + idx);
+        }
         }
     };
 
@@ -1359,6 +1493,19 @@ __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
 
     auto write_base_rows = [&]() { /* wave-private LDS; ordered for OTHER waves (gb0
                                       readers) by the round barrier that follows */
+        if constexpr (RL) {
+            /* gb[p] = my segment's first global slot, rf[p] = its first image slot:
+             * place needs no other wave's row */
+#pragma unroll
+            for (int k = 0; k < NBG; k++) {
+                uint32_t idx = (uint32_t)lane + k * WAVE;
+                if (idx < nparts) {
+                    gb[idx] = baser[NBG + k] + baser[k];
+                    rf[idx] = (uint16_t)(baser[2 * NBG + k] + baser[k]);
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < NBG; k++) {
             uint32_t idx = (uint32_t)lane + k * WAVE;
@@ -1414,7 +1561,8 @@ __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
             const uint32_t pid = pidr[g];
             const uint32_t rk = rankr[g];
             const uint32_t gd = gb[pid] + rk;
-            const uint32_t slot = (uint32_t)rf[pid] + (gd - gb0[pid]);
+            const uint32_t slot =
+                RL ? (uint32_t)rf[pid] + rk : (uint32_t)rf[pid] + (gd - gb0[pid]);
             dstg[slot] = gd;
             char *stage = stage0;
             hl_for<0, NC>([&](auto jc) {
@@ -1542,6 +1690,105 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_hash_count_seg(
         if (h) atomicAdd(&prow[p], h);
     }
     } /* segment loop */
+}
+
+/* K1 for the pre path, ROUND layout (DD_PRE_LAYOUT=round): one block per globally
+ * aligned round, W = blockDim.x / 64 waves, wave w owns segment r*W + w — the geometry of
+ * k_scatter_pre. The whole round is in one block's reach, so everything K3 needs below
+ * round granularity is produced here and the K2 scan runs over [nrounds][P] instead of
+ * [nseg][P] (16x fewer entries; no global atomics, no memset, no 120 MB gbase):
+ *   segoff[seg][p]  u16, row stride sP2: rows of partition p in the round's EARLIER
+ *                   segments (<= R - SEG); stored as packed dwords, 256 B per wave store
+ *   roundcnt[r][p]  u32, row stride sP2: the round's rows of partition p (scan input)
+ *   rofftab[r][p]   u16, row stride sP2: exclusive scan over p of roundcnt (the shfl
+ *                   scan k_round_roff runs on the seg layout)
+ * LDS: hist u32[W][sP2]; sP2 = P rounded up to even, and the pad column stays zero in
+ * every table. A ragged tail round counts only its real rows; segments past n_rows give
+ * zeros. */
+__global__ __launch_bounds__(16 * WAVE) void k_hash_count_round(
+    dd_kargs a, int64_t seg_rows, uint32_t nparts, uint32_t sP2, uint32_t *pid_out,
+    uint16_t *segoff, uint32_t *roundcnt, uint16_t *rofftab) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int W = (int)blockDim.x / WAVE;
+    const int wid = threadIdx.x / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    uint32_t *hist_all = (uint32_t *)smem;
+    uint32_t *hist = hist_all + (size_t)wid * sP2;
+    const int64_t r = blockIdx.x;
+    const int64_t seg = r * W + wid;
+
+    for (uint32_t p = lane; p < sP2; p += WAVE) hist[p] = 0;
+    /* single wave: LDS program order; no barrier */
+
+    const int64_t start = seg * seg_rows;
+    const int64_t end = (start + seg_rows < a.n_rows) ? start + seg_rows : a.n_rows;
+    /* as k_hash_count_seg: 4 independent row-groups per iteration, LDS atomicAdd counts */
+    for (int64_t base = start; base < end; base += 4 * WAVE) {
+        uint32_t pidu[4];
+        bool actu[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int64_t row = base + u * WAVE + lane;
+            actu[u] = row < end;
+            pidu[u] = 0;
+            if (actu[u]) {
+                uint64_t h = dd_row_hash(a, row);
+                const uint32_t totp = a.pid_total;
+                uint32_t fine = ((totp & (totp - 1)) == 0)
+                                    ? (uint32_t)(h & (uint64_t)(totp - 1))
+                                    : (uint32_t)(h % (uint64_t)totp);
+                pidu[u] = fine >> a.pid_shift;
+                if (a.pid8) ((uint8_t *)pid_out)[row] = (uint8_t)pidu[u];
+                else pid_out[row] = pidu[u];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            if (actu[u]) atomicAdd(&hist[pidu[u]], 1u);
+    }
+    __syncthreads(); /* the only barrier: below, histograms are read, never written */
+
+    /* each lane owns the partition pair (2d, 2d+1). Wave w sums the histograms of the
+     * waves before it (its segoff row); the last wave adds its own on top (the round's
+     * totals) and scans them over p. */
+    const uint2 *h2 = (const uint2 *)hist_all; /* row stride npair; sP2 even: 8 B aligned */
+    const uint32_t npair = sP2 / 2;
+    uint32_t *srow = (uint32_t *)(segoff + (size_t)seg * sP2);
+    uint2 *crow = (uint2 *)(roundcnt + (size_t)r * sP2);
+    uint32_t *orow = (uint32_t *)(rofftab + (size_t)r * sP2);
+    const bool last = wid == W - 1;
+    uint32_t carry = 0;
+    for (uint32_t d0 = 0; d0 < npair; d0 += WAVE) { /* wave-uniform trip count (shfl) */
+        const uint32_t d = d0 + lane;
+        const bool in = d < npair;
+        uint32_t s0 = 0, s1 = 0;
+        if (in) {
+            for (int w = 0; w < wid; w++) {
+                const uint2 v = h2[(size_t)w * npair + d];
+                s0 += v.x;
+                s1 += v.y;
+            }
+            srow[d] = s0 | (s1 << 16);
+        }
+        if (last) {
+            uint32_t c0 = 0, c1 = 0;
+            if (in) {
+                const uint2 v = h2[(size_t)wid * npair + d];
+                c0 = s0 + v.x;
+                c1 = s1 + v.y;
+                crow[d] = make_uint2(c0, c1);
+            }
+            uint32_t v = c0 + c1;
+#pragma unroll
+            for (int k = 1; k < WAVE; k <<= 1) {
+                uint32_t u = (uint32_t)__shfl_up((int)v, k);
+                if (lane >= k) v += u;
+            }
+            /* exclusive bases of 2d and 2d+1 (<= R: both fit u16) */
+            if (in) orow[d] = (carry + v - c0 - c1) | ((carry + v - c1) << 16);
+            carry += (uint32_t)__shfl((int)v, WAVE - 1);
+        }
+    }
 }
 
 /* K2d for the pre path: per-round image bases. counts must already be rewritten to
@@ -2209,6 +2456,52 @@ hipError_t dd_launch_hash_count_seg(const dd_kargs *a, int64_t nseg, int64_t seg
     return hipGetLastError();
 }
 
+hipError_t dd_launch_hash_count_round(const dd_kargs *a, int64_t nrounds, int64_t seg_rows,
+                                      int wpb, uint32_t nparts, uint32_t sP2,
+                                      uint32_t *pid_out, uint16_t *segoff,
+                                      uint32_t *roundcnt, uint16_t *rofftab,
+                                      hipStream_t s) {
+    /* full grid, one block per round (the capped-grid K1 is a recorded negative above) */
+    const size_t lds_bytes = (size_t)wpb * sP2 * 4; /* <= 16 * 512 * 4 */
+    hipLaunchKernelGGL(k_hash_count_round, dim3((unsigned)nrounds), dim3(wpb * WAVE),
+                       lds_bytes, s, *a, seg_rows, nparts, sP2, pid_out, segoff, roundcnt,
+                       rofftab);
+    return hipGetLastError();
+}
+
+/* round-granular K2: roundcnt[nrounds][sP2] -> rbase[nrounds][sP2] + part_offsets[P+1].
+ * The matrices carry sP2 columns (the zero pad column of an odd P is scanned along: its
+ * fold index P is part_offsets' last entry). nr2 == 0: one level (partial / combine /
+ * rewrite over nr1 ranges); else the nr1 range partials are scanned through nr2
+ * second-level ranges first. */
+hipError_t dd_launch_scan_round(const uint32_t *roundcnt, int64_t nrounds, uint32_t nparts,
+                                uint32_t sP2, int nr1, int nr2, uint32_t *partials,
+                                uint32_t *partials2, uint32_t *totals,
+                                uint64_t *part_offsets, uint32_t *rbase, hipStream_t s) {
+    const int threads = 256;
+    const int b1 = (int)(((int64_t)nr1 * sP2 + threads - 1) / threads);
+    const int bw = (int)((sP2 + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
+    hipLaunchKernelGGL(k_scan_partial_round, dim3(b1), dim3(threads), 0, s, roundcnt,
+                       nrounds, sP2, nr1, partials);
+    if (nr2 > 0) {
+        const int b2 = (int)(((int64_t)nr2 * sP2 + threads - 1) / threads);
+        hipLaunchKernelGGL(k_scan_partial_round, dim3(b2), dim3(threads), 0, s, partials,
+                           (int64_t)nr1, sP2, nr2, partials2);
+        hipLaunchKernelGGL(k_scan_combine_wave, dim3(bw), dim3(BLOCK_THREADS), 0, s,
+                           partials2, nr2, sP2, totals);
+        hipLaunchKernelGGL(k_scan_rewrite, dim3(b2), dim3(threads), 0, s, partials,
+                           (int64_t)nr1, sP2, nr2, partials2, nullptr);
+    } else {
+        hipLaunchKernelGGL(k_scan_combine_wave, dim3(bw), dim3(BLOCK_THREADS), 0, s,
+                           partials, nr1, sP2, totals);
+    }
+    hipLaunchKernelGGL(k_part_offsets, dim3(1), dim3(WAVE), 0, s, totals, nparts,
+                       part_offsets);
+    hipLaunchKernelGGL(k_scan_rewrite_rbase, dim3(b1), dim3(threads), 0, s, roundcnt,
+                       nrounds, sP2, nr1, partials, (const uint64_t *)part_offsets, rbase);
+    return hipGetLastError();
+}
+
 hipError_t dd_launch_round_layout(const uint32_t *counts, const uint64_t *part_offsets,
                                   int64_t nrounds, int wpb, uint32_t nparts, uint32_t sP2,
                                   uint16_t *rofftab, hipStream_t s) {
@@ -2221,9 +2514,12 @@ hipError_t dd_launch_round_layout(const uint32_t *counts, const uint64_t *part_o
 hipError_t dd_launch_scatter_pre(const dd_kargs *a, int64_t nblocks, int64_t nrounds,
                                  int rpb, uint32_t nparts, int nbits,
                                  const uint32_t *pid_in, const uint32_t *gbase,
-                                 const uint16_t *rofftab, uint32_t sP2, int gmax, int wpb,
-                                 size_t lds_bytes, hipStream_t s) {
+                                 const uint16_t *rofftab, uint32_t sP2,
+                                 const uint16_t *segoff, const uint32_t *rbase, int layout,
+                                 int xcd, int gmax, int wpb, size_t lds_bytes,
+                                 hipStream_t s) {
     dim3 grid((unsigned)nblocks);
+    const bool rl = layout == 2; /* round layout reads segoff/rbase, seg layout gbase */
     const int n = a->n_cols;
     auto el = [&](int c) { return (int)a->cols[c].elem; };
 #define DD_PREW(GM, W_, NBG_, NBI_, ...)                                                     \
@@ -2234,15 +2530,17 @@ hipError_t dd_launch_scatter_pre(const dd_kargs *a, int64_t nblocks, int64_t nro
                   nparts <= (uint32_t)(NBG_ * WAVE));                                        \
         for (int c = 0; c < wn && m; c++) m = el(c) == want[c];                              \
         if (m) {                                                                             \
+            auto kfn = rl ? k_scatter_pre<true, GM, W_, NBG_, NBI_, __VA_ARGS__>             \
+                          : k_scatter_pre<false, GM, W_, NBG_, NBI_, __VA_ARGS__>;           \
             if (lds_bytes > 65536) {                                                         \
                 hipError_t e = hipFuncSetAttribute(                                          \
-                    (const void *)k_scatter_pre<GM, W_, NBG_, NBI_, __VA_ARGS__>,            \
-                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);             \
+                    (const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,           \
+                    (int)lds_bytes);                                                         \
                 if (e != hipSuccess) return e;                                               \
             }                                                                                \
-            hipLaunchKernelGGL((k_scatter_pre<GM, W_, NBG_, NBI_, __VA_ARGS__>), grid,       \
-                               dim3(W_ * WAVE), lds_bytes, s, *a, nrounds, rpb, nparts,      \
-                               nbits, pid_in, gbase, rofftab, sP2);                          \
+            hipLaunchKernelGGL(kfn, grid, dim3(W_ * WAVE), lds_bytes, s, *a, nrounds, rpb,   \
+                               nparts, nbits, pid_in, gbase, rofftab, sP2, segoff, rbase,    \
+                               xcd);                                                         \
             return hipGetLastError();                                                        \
         }                                                                                    \
     }

@@ -144,6 +144,14 @@ typedef struct dd_partitioner_info {
     int64_t n_launch;   /* nchunks (v1/staged) or nrounds (pre) */
 } dd_partitioner_info;
 dd_status dd_partitioner_get_info(const dd_partitioner *p, dd_partitioner_info *out);
+/* how the pre path precomputes its scatter layout: 0 = not the pre path, 1 = per wave
+ * segment (k_hash_count_seg + segment-granular scan), 2 = per round (k_hash_count_round +
+ * round-granular scan). Kept out of dd_partitioner_info, whose size is part of the ABI. */
+int32_t dd_partitioner_pre_layout(const dd_partitioner *p);
+/* out[b] = logical block of hardware block b in a grid of `nblocks` under DD_PRE_XCD=1
+ * (hardware blocks with equal b mod 8 get one contiguous run of logical blocks); runs on
+ * the host, so the map can be checked without a device */
+void dd_pre_xcd_block_map(int64_t nblocks, int64_t *out);
 
 /* result accessors (pointers are device memory owned by the partitioner) */
 /* u32[n_rows] of per-row partition ids. NULL ONLY when the opt-in DD_RHASH=1 recompute
