@@ -388,6 +388,12 @@ class Partitioner:
         (dd_partitioner_pre_layout; DD_PRE_LAYOUT=seg|round at create time)."""
         return int(lib().dd_partitioner_pre_layout(self.h))
 
+    def k1_spec(self):
+        """Key-signature code of the K1 hash/count kernel: 0 = generic run-time key loop,
+        else kind(key 0) | kind(key 1) << 4 (dd_partitioner_k1_spec; DD_K1_SPEC=0 at
+        create time forces 0)."""
+        return int(lib().dd_partitioner_k1_spec(self.h))
+
     def has_pid_array(self):
         """Fast null-check of the device pid pointer (no download): False when the spec
         path recomputes hashes in-kernel (rhash) and no pid array exists."""

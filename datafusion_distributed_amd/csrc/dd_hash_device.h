@@ -94,6 +94,128 @@ __device__ __forceinline__ uint64_t dd_row_hash(const dd_kargs &a, int64_t i) {
     return h;
 }
 
+/* ---------------- K1 with a compile-time key signature ----------------
+ * dd_row_hash walks a.n_keys at run time and switches on the dtype per row, so a K1 loop
+ * "unrolled over G row groups" compiles to G copies of load -> wait -> hash -> store: one
+ * key load in flight per lane. With the signature (the kinds of one or two NON-NULLABLE
+ * fixed-width key columns) known at compile time the body is straight-line code and every
+ * key load of every group issues before the first wait. The host picks the signature once
+ * (dd_partitioner_create; dd_partitioner_k1_spec reports it); everything it does not
+ * whitelist keeps dd_row_hash. Kinds and codes: DD_KK_* / DD_K1_CODE in dd_internal.h. */
+
+template <int K> struct dd_kk_raw { using T = uint8_t; };
+template <> struct dd_kk_raw<DD_KK_B2> { using T = uint16_t; };
+template <> struct dd_kk_raw<DD_KK_B4> { using T = uint32_t; };
+template <> struct dd_kk_raw<DD_KK_B8> { using T = uint64_t; };
+template <> struct dd_kk_raw<DD_KK_F32> { using T = float; };
+template <> struct dd_kk_raw<DD_KK_F64> { using T = double; };
+template <> struct dd_kk_raw<DD_KK_DICT32> { using T = int32_t; };
+
+/* value hash of a loaded key element (dict32: v is the index, gathered by the caller) */
+template <int K>
+__device__ __forceinline__ uint64_t dd_kk_hash(typename dd_kk_raw<K>::T v) {
+    if constexpr (K == DD_KK_F32) return dd_mix64(dd_canon_f32_dev(v));
+    else if constexpr (K == DD_KK_F64) return dd_mix64(dd_canon_f64_dev(v));
+    else return dd_mix64((uint64_t)v); /* unsigned raw types: zero-extended, as the oracle */
+}
+
+/* K1 work of G row groups: rows row0 + g * stride, g < G, those below `end` active
+ * (end > 0; at least the caller's first row is below it). Order: clamp -> all key loads ->
+ * dict32 gathers -> hashes -> pid rule -> pid stores -> LDS counts. An inactive lane
+ * loads row end - 1 (as k_scatter_pre::preload clamps), so no load sits under a branch. */
+template <int K0, int K1, int G>
+__device__ __forceinline__ void dd_k1_spec_groups(const dd_kargs &a, int64_t row0,
+                                                  int64_t stride, int64_t end,
+                                                  uint32_t *pid_out, uint32_t *hist) {
+    using T0 = typename dd_kk_raw<K0>::T;
+    using T1 = typename dd_kk_raw<K1>::T;
+    constexpr bool TWO = K1 != DD_KK_NONE;
+    const dd_kcol &c0 = a.cols[a.key_idx[0]];
+    const dd_kcol &c1 = a.cols[a.key_idx[TWO ? 1 : 0]];
+    const T0 *__restrict__ d0 = (const T0 *)c0.data;
+    const T1 *__restrict__ d1 = (const T1 *)c1.data;
+
+    int64_t row[G], crow[G];
+    bool act[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        row[g] = row0 + g * stride;
+        act[g] = row[g] < end;
+        crow[g] = act[g] ? row[g] : end - 1;
+    }
+    T0 r0[G];
+    T1 r1[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) r0[g] = d0[crow[g]];
+    if constexpr (TWO) {
+#pragma unroll
+        for (int g = 0; g < G; g++) r1[g] = d1[crow[g]];
+    }
+    /* nothing moves across: left alone, the scheduler hoists the first group's hash (and
+     * with it a wait) above the later groups' loads */
+    __builtin_amdgcn_sched_barrier(0);
+    uint64_t v0[G], v1[G];
+    if constexpr (K0 == DD_KK_DICT32) {
+        const uint64_t *__restrict__ dh = c0.dict_hashes;
+#pragma unroll
+        for (int g = 0; g < G; g++) v0[g] = dh[r0[g]];
+        __builtin_amdgcn_sched_barrier(0);
+    } else {
+#pragma unroll
+        for (int g = 0; g < G; g++) v0[g] = dd_kk_hash<K0>(r0[g]);
+    }
+    if constexpr (TWO) {
+        static_assert(K1 != DD_KK_DICT32, "dict32 is instantiated as a single key only");
+#pragma unroll
+        for (int g = 0; g < G; g++) v1[g] = dd_kk_hash<K1>(r1[g]);
+    }
+    /* dd_row_hash's combine; its first step from h = 0 is vh + golden */
+    uint64_t h[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        h[g] = v0[g] + 0x9e3779b97f4a7c15ULL;
+        if constexpr (TWO)
+            h[g] = h[g] ^ (v1[g] + 0x9e3779b97f4a7c15ULL + (h[g] << 6) + (h[g] >> 2));
+    }
+    /* pid = (h % pid_total) >> pid_shift */
+    const uint32_t tot = a.pid_total;
+    uint32_t pid[G];
+    if ((tot & (tot - 1)) == 0) {
+#pragma unroll
+        for (int g = 0; g < G; g++) pid[g] = (uint32_t)(h[g] & (uint64_t)(tot - 1));
+    } else {
+#pragma unroll
+        for (int g = 0; g < G; g++) pid[g] = (uint32_t)(h[g] % (uint64_t)tot);
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) pid[g] >>= a.pid_shift;
+    if (a.pid8) {
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            if (act[g]) ((uint8_t *)pid_out)[row[g]] = (uint8_t)pid[g];
+    } else {
+#pragma unroll
+        for (int g = 0; g < G; g++)
+            if (act[g]) pid_out[row[g]] = pid[g];
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++)
+        if (act[g]) atomicAdd(&hist[pid[g]], 1u);
+}
+
+/* one K1 iteration of a wave segment or block tile: 4 groups, or 2 where no more than two
+ * groups' worth of rows is left (the SEG = 128 tiers; a short tail) */
+template <int K0, int K1>
+__device__ __forceinline__ void dd_k1_spec_iter(const dd_kargs &a, int64_t base, int lane,
+                                                int64_t stride, int64_t end,
+                                                uint32_t *pid_out, uint32_t *hist) {
+    /* wave-uniform in every caller; said so, the choice is a scalar branch */
+    if (__builtin_amdgcn_readfirstlane((int)(end - base <= 2 * stride)))
+        dd_k1_spec_groups<K0, K1, 2>(a, base + lane, stride, end, pid_out, hist);
+    else
+        dd_k1_spec_groups<K0, K1, 4>(a, base + lane, stride, end, pid_out, hist);
+}
+
 /* ballot-multisplit: lanes with equal pid (among `act`); returns the equal-mask */
 __device__ __forceinline__ uint64_t dd_eq_mask(uint32_t pid, uint64_t act, int nbits) {
     uint64_t eq = act;

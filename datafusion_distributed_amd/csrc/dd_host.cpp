@@ -144,6 +144,7 @@ struct dd_partitioner {
     int pre_layout = 0; /* 0 not pre, 1 seg (k_hash_count_seg), 2 round (k_hash_count_round) */
     int pre_xcd = 0;    /* DD_PRE_XCD=1: k_scatter_pre walks rounds in XCD-contiguous order */
     int round_nr1 = 0, round_nr2 = 0; /* round layout: scan ranges (nr2 == 0: one level) */
+    int k1_spec = 0; /* K1 key-signature code (DD_K1_CODE; 0 = generic dd_row_hash body) */
 
     /* device buffers (owned) */
     uint32_t *pid = nullptr;
@@ -552,6 +553,37 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
             ka.hl = 2;
     }
 
+    /* K1 key signature (dd_hash_device.h): the tile / seg / round K1
+     * kernels are instantiated for one or two non-nullable fixed-width keys of the kinds
+     * below, where every key load of a wave's row groups issues before the first wait.
+     * Anything else (a validity buffer on a key, utf8, three or more keys, other pairs),
+     * the v1 path, and rhash (no pid array to store to) keep the generic body.
+     * DD_K1_SPEC=0 forces the generic body for A/B. Must mirror DD_K1_TABLE. */
+    if (p->staged && !ka.rhash && !(getenv("DD_K1_SPEC") && atoi(getenv("DD_K1_SPEC")) == 0)) {
+        auto kind = [&](int k) {
+            const dd_col_desc &cd = batch->cols[key_cols[k]];
+            if (cd.validity) return (int)DD_KK_NONE;
+            switch (cd.dtype) {
+            case DD_DT_U8:
+            case DD_DT_BOOL: return (int)DD_KK_B1;
+            case DD_DT_I16: return (int)DD_KK_B2;
+            case DD_DT_I32: return (int)DD_KK_B4;
+            case DD_DT_I64: return (int)DD_KK_B8;
+            case DD_DT_F32: return (int)DD_KK_F32;
+            case DD_DT_F64: return (int)DD_KK_F64;
+            case DD_DT_DICT32: return (int)DD_KK_DICT32;
+            default: return (int)DD_KK_NONE;
+            }
+        };
+        if (n_keys == 1) {
+            p->k1_spec = DD_K1_CODE(kind(0), DD_KK_NONE);
+        } else if (n_keys == 2) {
+            const int k0 = kind(0), k1 = kind(1);
+            if ((k0 == DD_KK_B8 && k1 == DD_KK_B4) || (k0 == DD_KK_B1 && k1 == DD_KK_B1))
+                p->k1_spec = DD_K1_CODE(k0, k1);
+        }
+    }
+
     auto halloc = [&](void **ptr, size_t bytes) {
         return hipMalloc(ptr, bytes > 0 ? bytes : 1) == hipSuccess;
     };
@@ -727,16 +759,16 @@ extern "C" dd_status dd_partitioner_run_phase1(dd_partitioner *p, void *stream) 
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipEventRecord(p->ev[0], s));
     if (p->pre_layout == 2) {
-        HIP_TRY(dd_launch_hash_count_round(&p->ka, p->nrounds, p->chunk_rows, p->wpb,
+        HIP_TRY(dd_launch_hash_count_round(&p->ka, p->k1_spec, p->nrounds, p->chunk_rows, p->wpb,
                                            p->nparts, p->sP2, p->pid, p->counts16,
                                            p->roundcnt, p->imgb, s));
     } else if (p->pre) {
         HIP_TRY(hipMemsetAsync(p->partials, 0, (size_t)p->pre_nranges * p->nparts * 4, s));
-        HIP_TRY(dd_launch_hash_count_seg(&p->ka, p->nseg_pad, p->chunk_rows, p->nparts,
+        HIP_TRY(dd_launch_hash_count_seg(&p->ka, p->k1_spec, p->nseg_pad, p->chunk_rows, p->nparts,
                                          p->nbits, p->pid, p->counts16, p->partials,
                                          p->pre_nranges, p->lds_k1, s));
     } else if (p->staged) {
-        HIP_TRY(dd_launch_hash_count_tile(&p->ka, p->nchunks, p->chunk_rows, p->nparts,
+        HIP_TRY(dd_launch_hash_count_tile(&p->ka, p->k1_spec, p->nchunks, p->chunk_rows, p->nparts,
                                           p->nbits, p->pid, p->counts, p->lds_k1, s));
     } else {
         HIP_TRY(dd_launch_hash_count(&p->ka, p->nchunks, p->chunk_rows, p->nparts, p->nbits,
@@ -850,6 +882,10 @@ extern "C" int32_t dd_partitioner_pid_elem(const dd_partitioner *p) {
 
 extern "C" int32_t dd_partitioner_pre_layout(const dd_partitioner *p) {
     return p ? p->pre_layout : 0;
+}
+
+extern "C" int32_t dd_partitioner_k1_spec(const dd_partitioner *p) {
+    return p ? p->k1_spec : 0;
 }
 
 extern "C" void dd_pre_xcd_block_map(int64_t nblocks, int64_t *out) {

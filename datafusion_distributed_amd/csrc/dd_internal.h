@@ -37,6 +37,21 @@ enum {
     DD_KDT_ROWID = 101,  /* synthetic (staged-var): value = input row index */
 };
 
+/* K1 key kinds: what a compile-time key signature (dd_hash_device.h) says about one
+ * non-nullable key column */
+enum {
+    DD_KK_NONE = 0,
+    DD_KK_B1 = 1, /* u8 / bool */
+    DD_KK_B2 = 2, /* i16 */
+    DD_KK_B4 = 3, /* i32 */
+    DD_KK_B8 = 4, /* i64 */
+    DD_KK_F32 = 5,
+    DD_KK_F64 = 6,
+    DD_KK_DICT32 = 7,
+};
+/* signature code: first key's kind | second key's kind << 4 (0 = generic body) */
+#define DD_K1_CODE(K0, K1) ((K0) | ((K1) << 4))
+
 struct dd_kcol {
     int32_t dtype;
     int32_t elem;               /* fixed elem size (1/2/4/8); 0 for var (utf8) data */
@@ -144,10 +159,11 @@ hipError_t dd_launch_scan(uint32_t *counts, int64_t nchunks, uint32_t nparts, in
 hipError_t dd_launch_scan_deep(uint16_t *counts16, int64_t nchunks, uint32_t nparts,
                                int nr1, int nr2, uint32_t *partials, uint32_t *partials2,
                                uint64_t *part_offsets, uint32_t *gbase, hipStream_t s);
-hipError_t dd_launch_hash_count_seg(const dd_kargs *a, int64_t nseg, int64_t seg_rows,
-                                    uint32_t nparts, int nbits, uint32_t *pid_out,
-                                    uint16_t *counts, uint32_t *partials, int nranges,
-                                    size_t lds_bytes, hipStream_t s);
+/* k1_spec: the K1 key-signature code chosen at create time (dd_hash_device.h; 0 = generic) */
+hipError_t dd_launch_hash_count_seg(const dd_kargs *a, int k1_spec, int64_t nseg,
+                                    int64_t seg_rows, uint32_t nparts, int nbits,
+                                    uint32_t *pid_out, uint16_t *counts, uint32_t *partials,
+                                    int nranges, size_t lds_bytes, hipStream_t s);
 hipError_t dd_launch_round_layout(const uint32_t *counts, const uint64_t *part_offsets,
                                   int64_t nrounds, int wpb, uint32_t nparts, uint32_t sP2,
                                   uint16_t *imgb, hipStream_t s);
@@ -157,18 +173,19 @@ hipError_t dd_launch_scatter_pre(const dd_kargs *a, int64_t nblocks, int64_t nro
                                  const uint16_t *imgb, uint32_t sP2, const uint16_t *segoff,
                                  const uint32_t *rbase, int layout, int xcd, int gmax,
                                  int wpb, size_t lds_bytes, hipStream_t s);
-hipError_t dd_launch_hash_count_round(const dd_kargs *a, int64_t nrounds, int64_t seg_rows,
-                                      int wpb, uint32_t nparts, uint32_t sP2,
-                                      uint32_t *pid_out, uint16_t *segoff,
+hipError_t dd_launch_hash_count_round(const dd_kargs *a, int k1_spec, int64_t nrounds,
+                                      int64_t seg_rows, int wpb, uint32_t nparts,
+                                      uint32_t sP2, uint32_t *pid_out, uint16_t *segoff,
                                       uint32_t *roundcnt, uint16_t *rofftab,
                                       hipStream_t s);
 hipError_t dd_launch_scan_round(const uint32_t *roundcnt, int64_t nrounds, uint32_t nparts,
                                 uint32_t sP2, int nr1, int nr2, uint32_t *partials,
                                 uint32_t *partials2, uint32_t *totals,
                                 uint64_t *part_offsets, uint32_t *rbase, hipStream_t s);
-hipError_t dd_launch_hash_count_tile(const dd_kargs *a, int64_t nblocks, int64_t tile_rows,
-                                     uint32_t nparts, int nbits, uint32_t *pid_out,
-                                     uint32_t *counts, size_t lds_bytes, hipStream_t s);
+hipError_t dd_launch_hash_count_tile(const dd_kargs *a, int k1_spec, int64_t nblocks,
+                                     int64_t tile_rows, uint32_t nparts, int nbits,
+                                     uint32_t *pid_out, uint32_t *counts, size_t lds_bytes,
+                                     hipStream_t s);
 hipError_t dd_launch_scatter_staged(const dd_kargs *a, int64_t nblocks, int64_t tile_rows,
                                     uint32_t nparts, int nbits, const uint32_t *pid_in,
                                     const uint32_t *tile_off, const uint64_t *part_offsets,

@@ -394,6 +394,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_scatter(
  * order == (wave, group, lane) order — stability preserved vs the oracle). Fixed-width
  * columns only; batches with var-width columns take the v1 path. */
 
+/* K0/K1: compile-time key signature (dd_hash_device.h); K0 = DD_KK_NONE is the generic
+ * body */
+template <int K0, int K1>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_hash_count_tile(
     dd_kargs a, int64_t tile_rows, uint32_t nparts, int nbits, uint32_t *pid_out,
     uint32_t *counts /* [nblocks][P] */) {
@@ -410,8 +413,14 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_hash_count_tile(
     const int64_t tstart = (int64_t)blockIdx.x * tile_rows;
     const int64_t tend = (tstart + tile_rows < a.n_rows) ? (tstart + tile_rows) : a.n_rows;
 
-    /* 2 independent row-groups per iteration: doubles loads in flight per wave and
-     * halves the serialized LDS-histogram chain per row */
+    if constexpr (K0 != DD_KK_NONE) {
+        /* 4 row groups per iteration, every key load issued before the first wait */
+        for (int64_t base = tstart; base < tend; base += 4 * BLOCK_THREADS)
+            dd_k1_spec_iter<K0, K1>(a, base, tid, BLOCK_THREADS, tend, pid_out, myhist);
+    } else
+    /* generic keys: 2 row groups per iteration. dd_row_hash's run-time key loop keeps the
+     * groups serialised (load, wait, hash, store per group), so this halves the LDS
+     * histogram chain per row but does not overlap the loads */
     for (int64_t base = tstart; base < tend; base += 2 * BLOCK_THREADS) {
         uint32_t pidu[2];
         bool actu[2];
@@ -1626,7 +1635,9 @@ __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
  * of a globally-aligned round). 4 segments per 256-thread block; per-wave LDS hist.
  * Fuses the first scan pass: each wave atomicAdds its histogram into its range row of
  * `partials` (zeroed by the host first), so dd_launch_scan_deep skips k_scan_partial's
- * full re-read of counts. a.pid8=1 stores pids as u8. */
+ * full re-read of counts. a.pid8=1 stores pids as u8. K0/K1: compile-time key signature
+ * (dd_hash_device.h); K0 = DD_KK_NONE is the generic body. */
+template <int K0, int K1>
 __global__ __launch_bounds__(BLOCK_THREADS) void k_hash_count_seg(
     dd_kargs a, int64_t nseg, int64_t seg_rows, uint32_t nparts, int nbits,
     uint32_t *pid_out, uint16_t *counts /* [nseg][P]; seg counts <= SEG <= 1024: u16
@@ -1651,8 +1662,14 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_hash_count_seg(
     const int64_t start = seg * seg_rows;
     const int64_t end = (start + seg_rows < a.n_rows) ? start + seg_rows : a.n_rows;
 
-    /* 4 independent row-groups per iteration (SEG = 256 at G4: the whole segment in one
-     * iteration) — doubles the loads in flight vs the tile kernel's 2-group form */
+    if constexpr (K0 != DD_KK_NONE) {
+        /* 4 row groups per iteration (SEG = 256 at G4: the whole segment in one), every
+         * key load issued before the first wait */
+        for (int64_t base = start; base < end; base += 4 * WAVE)
+            dd_k1_spec_iter<K0, K1>(a, base, lane, WAVE, end, pid_out, hist);
+    } else
+    /* generic keys: 4 row groups per iteration, which dd_row_hash's run-time key loop
+     * keeps serialised (load, wait, hash, store per group) */
     for (int64_t base = start; base < end; base += 4 * WAVE) {
         uint32_t pidu[4];
         bool actu[4];
@@ -1704,7 +1721,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_hash_count_seg(
  *                   scan k_round_roff runs on the seg layout)
  * LDS: hist u32[W][sP2]; sP2 = P rounded up to even, and the pad column stays zero in
  * every table. A ragged tail round counts only its real rows; segments past n_rows give
- * zeros. */
+ * zeros. K0/K1: compile-time key signature (dd_hash_device.h); K0 = DD_KK_NONE is the
+ * generic body. */
+template <int K0, int K1>
 __global__ __launch_bounds__(16 * WAVE) void k_hash_count_round(
     dd_kargs a, int64_t seg_rows, uint32_t nparts, uint32_t sP2, uint32_t *pid_out,
     uint16_t *segoff, uint32_t *roundcnt, uint16_t *rofftab) {
@@ -1722,7 +1741,12 @@ __global__ __launch_bounds__(16 * WAVE) void k_hash_count_round(
 
     const int64_t start = seg * seg_rows;
     const int64_t end = (start + seg_rows < a.n_rows) ? start + seg_rows : a.n_rows;
-    /* as k_hash_count_seg: 4 independent row-groups per iteration, LDS atomicAdd counts */
+    /* as k_hash_count_seg: with a key signature the groups' loads overlap, the generic
+     * body runs them one after the other; LDS atomicAdd counts either way */
+    if constexpr (K0 != DD_KK_NONE) {
+        for (int64_t base = start; base < end; base += 4 * WAVE)
+            dd_k1_spec_iter<K0, K1>(a, base, lane, WAVE, end, pid_out, hist);
+    } else
     for (int64_t base = start; base < end; base += 4 * WAVE) {
         uint32_t pidu[4];
         bool actu[4];
@@ -2435,38 +2459,66 @@ hipError_t dd_launch_scan_deep(uint16_t *counts16, int64_t nchunks, uint32_t npa
     return hipGetLastError();
 }
 
-hipError_t dd_launch_hash_count_seg(const dd_kargs *a, int64_t nseg, int64_t seg_rows,
-                                    uint32_t nparts, int nbits, uint32_t *pid_out,
-                                    uint16_t *counts, uint32_t *partials, int nranges,
-                                    size_t lds_bytes, hipStream_t s) {
+/* K1 key signatures (dd_hash_device.h): the instantiations of the three K1 kernels. Must
+ * mirror the signature choice in dd_partitioner_create (dd_host.cpp); a code outside the
+ * table is a launch error. */
+#define DD_K1_TABLE(X)                                                                       \
+    X(DD_KK_NONE, DD_KK_NONE)   /* generic body */                                           \
+    X(DD_KK_B1, DD_KK_NONE)                                                                  \
+    X(DD_KK_B2, DD_KK_NONE)                                                                  \
+    X(DD_KK_B4, DD_KK_NONE)                                                                  \
+    X(DD_KK_B8, DD_KK_NONE)     /* headline */                                               \
+    X(DD_KK_F32, DD_KK_NONE)                                                                 \
+    X(DD_KK_F64, DD_KK_NONE)                                                                 \
+    X(DD_KK_DICT32, DD_KK_NONE) /* dictkey */                                                \
+    X(DD_KK_B8, DD_KK_B4)       /* multikey */                                               \
+    X(DD_KK_B1, DD_KK_B1)       /* q1 */
+
+hipError_t dd_launch_hash_count_seg(const dd_kargs *a, int k1_spec, int64_t nseg,
+                                    int64_t seg_rows, uint32_t nparts, int nbits,
+                                    uint32_t *pid_out, uint16_t *counts, uint32_t *partials,
+                                    int nranges, size_t lds_bytes, hipStream_t s) {
     /* full grid (one segment per wave): a capped grid with consecutive-segment runs
      * per wave measured K1 0.26 -> 0.40 ms — the dense all-waves-in-one-row-window
      * layout wins (DRAM page locality), dispatch overhead is not the cost */
     int64_t nblk = nseg / WAVES_PER_BLOCK;
     if (nblk < 1) nblk = 1;
     dim3 grid((unsigned)nblk);
-    if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_hash_count_seg,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes);
-        if (e != hipSuccess) return e;
+#define DD_K1SEG(K0_, K1_)                                                                   \
+    if (k1_spec == DD_K1_CODE(K0_, K1_)) {                                                   \
+        auto kfn = k_hash_count_seg<K0_, K1_>;                                               \
+        if (lds_bytes > 65536) {                                                             \
+            hipError_t e = hipFuncSetAttribute(                                              \
+                (const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,               \
+                (int)lds_bytes);                                                             \
+            if (e != hipSuccess) return e;                                                   \
+        }                                                                                    \
+        hipLaunchKernelGGL(kfn, grid, dim3(BLOCK_THREADS), lds_bytes, s, *a, nseg, seg_rows, \
+                           nparts, nbits, pid_out, counts, partials, nranges);               \
+        return hipGetLastError();                                                            \
     }
-    hipLaunchKernelGGL(k_hash_count_seg, grid, dim3(BLOCK_THREADS), lds_bytes, s, *a, nseg,
-                       seg_rows, nparts, nbits, pid_out, counts, partials, nranges);
-    return hipGetLastError();
+    DD_K1_TABLE(DD_K1SEG)
+#undef DD_K1SEG
+    return hipErrorInvalidValue;
 }
 
-hipError_t dd_launch_hash_count_round(const dd_kargs *a, int64_t nrounds, int64_t seg_rows,
-                                      int wpb, uint32_t nparts, uint32_t sP2,
-                                      uint32_t *pid_out, uint16_t *segoff,
+hipError_t dd_launch_hash_count_round(const dd_kargs *a, int k1_spec, int64_t nrounds,
+                                      int64_t seg_rows, int wpb, uint32_t nparts,
+                                      uint32_t sP2, uint32_t *pid_out, uint16_t *segoff,
                                       uint32_t *roundcnt, uint16_t *rofftab,
                                       hipStream_t s) {
     /* full grid, one block per round (the capped-grid K1 is a recorded negative above) */
     const size_t lds_bytes = (size_t)wpb * sP2 * 4; /* <= 16 * 512 * 4 */
-    hipLaunchKernelGGL(k_hash_count_round, dim3((unsigned)nrounds), dim3(wpb * WAVE),
-                       lds_bytes, s, *a, seg_rows, nparts, sP2, pid_out, segoff, roundcnt,
-                       rofftab);
-    return hipGetLastError();
+#define DD_K1ROUND(K0_, K1_)                                                                 \
+    if (k1_spec == DD_K1_CODE(K0_, K1_)) {                                                   \
+        hipLaunchKernelGGL((k_hash_count_round<K0_, K1_>), dim3((unsigned)nrounds),          \
+                           dim3(wpb * WAVE), lds_bytes, s, *a, seg_rows, nparts, sP2,        \
+                           pid_out, segoff, roundcnt, rofftab);                              \
+        return hipGetLastError();                                                            \
+    }
+    DD_K1_TABLE(DD_K1ROUND)
+#undef DD_K1ROUND
+    return hipErrorInvalidValue;
 }
 
 /* round-granular K2: roundcnt[nrounds][sP2] -> rbase[nrounds][sP2] + part_offsets[P+1].
@@ -2582,18 +2634,26 @@ hipError_t dd_launch_scatter_pre(const dd_kargs *a, int64_t nblocks, int64_t nro
     return hipErrorInvalidValue;
 }
 
-hipError_t dd_launch_hash_count_tile(const dd_kargs *a, int64_t nblocks, int64_t tile_rows,
-                                     uint32_t nparts, int nbits, uint32_t *pid_out,
-                                     uint32_t *counts, size_t lds_bytes, hipStream_t s) {
-    if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_hash_count_tile,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes);
-        if (e != hipSuccess) return e;
+hipError_t dd_launch_hash_count_tile(const dd_kargs *a, int k1_spec, int64_t nblocks,
+                                     int64_t tile_rows, uint32_t nparts, int nbits,
+                                     uint32_t *pid_out, uint32_t *counts, size_t lds_bytes,
+                                     hipStream_t s) {
+#define DD_K1TILE(K0_, K1_)                                                                  \
+    if (k1_spec == DD_K1_CODE(K0_, K1_)) {                                                   \
+        auto kfn = k_hash_count_tile<K0_, K1_>;                                              \
+        if (lds_bytes > 65536) {                                                             \
+            hipError_t e = hipFuncSetAttribute(                                              \
+                (const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,               \
+                (int)lds_bytes);                                                             \
+            if (e != hipSuccess) return e;                                                   \
+        }                                                                                    \
+        hipLaunchKernelGGL(kfn, dim3((unsigned)nblocks), dim3(BLOCK_THREADS), lds_bytes, s,  \
+                           *a, tile_rows, nparts, nbits, pid_out, counts);                   \
+        return hipGetLastError();                                                            \
     }
-    hipLaunchKernelGGL(k_hash_count_tile, dim3((unsigned)nblocks), dim3(BLOCK_THREADS),
-                       lds_bytes, s, *a, tile_rows, nparts, nbits, pid_out, counts);
-    return hipGetLastError();
+    DD_K1_TABLE(DD_K1TILE)
+#undef DD_K1TILE
+    return hipErrorInvalidValue;
 }
 
 hipError_t dd_launch_scatter_staged(const dd_kargs *a, int64_t nblocks, int64_t tile_rows,

@@ -148,6 +148,12 @@ dd_status dd_partitioner_get_info(const dd_partitioner *p, dd_partitioner_info *
  * segment (k_hash_count_seg + segment-granular scan), 2 = per round (k_hash_count_round +
  * round-granular scan). Kept out of dd_partitioner_info, whose size is part of the ABI. */
 int32_t dd_partitioner_pre_layout(const dd_partitioner *p);
+/* the compile-time key signature the K1 hash/count kernel runs with: 0 = the generic
+ * run-time key loop; otherwise kind(key 0) | kind(key 1) << 4 with kinds 1 u8/bool, 2 i16,
+ * 3 i32, 4 i64, 5 f32, 6 f64, 7 dict32. Chosen at create time for one non-nullable key of
+ * those kinds and the pairs i64+i32 and u8/bool+u8/bool on the staged and pre paths
+ * (ranged partitioners included); DD_K1_SPEC=0 forces 0. Results do not depend on it. */
+int32_t dd_partitioner_k1_spec(const dd_partitioner *p);
 /* out[b] = logical block of hardware block b in a grid of `nblocks` under DD_PRE_XCD=1
  * (hardware blocks with equal b mod 8 get one contiguous run of logical blocks); runs on
  * the host, so the map can be checked without a device */

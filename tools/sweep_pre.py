@@ -1,4 +1,4 @@
-"""Interleaved one-box A/B of the K3 scatter variants on a bench shape.
+"""Interleaved one-box A/B of the K1 / K3 variants on a bench shape.
 
 Sequential per-config blocks measured ±4-5% within-box drift (clock/thermal), swamping
 the ~3-6% deltas under test. This sweep creates every config's partitioner up-front
@@ -37,12 +37,14 @@ CONFIGS = [
     ("pre-rpb1", {"DD_PRE_RPB": "1"}),
     ("pre-rpb4", {"DD_PRE_RPB": "4"}),
     ("plain", {"DD_K3_PRE": "0", "DD_K3_HL": "0"}),
+    ("spec", {}),                       # the default: K1 with its compile-time key signature
+    ("generic", {"DD_K1_SPEC": "0"}),   # K1 with the run-time key loop
 ]
 if len(sys.argv) > 4:
     CONFIGS = [c for c in CONFIGS if c[0] in sys.argv[4].split(",")]
 
 KNOBS = ["DD_K3_PRE", "DD_K3_HL", "DD_PID8", "DD_PRE_NT", "DD_PRE_RPB", "DD_PRE_GMAX",
-         "DD_PRE_WPB", "DD_PRE_LAYOUT", "DD_PRE_XCD"]
+         "DD_PRE_WPB", "DD_PRE_LAYOUT", "DD_PRE_XCD", "DD_K1_SPEC"]
 
 
 def main():
@@ -56,7 +58,8 @@ def main():
         os.environ.update(env)
         part = api.Partitioner(batch, key_idx, P)
         parts.append((name, part))
-        print(name, "plan", json.dumps({**part.info(), "pre_layout": part.pre_layout()}),
+        print(name, "plan", json.dumps({**part.info(), "pre_layout": part.pre_layout(),
+                                        "k1_spec": part.k1_spec()}),
               flush=True)
     samples = {name: [] for name, _ in CONFIGS}
     for r in range(REPS + 2):
