@@ -388,6 +388,12 @@ class Partitioner:
         (dd_partitioner_pre_layout; DD_PRE_LAYOUT=seg|round at create time)."""
         return int(lib().dd_partitioner_pre_layout(self.h))
 
+    def pre_wide(self):
+        """1 when the pre path scatters in wide rounds (8192 rows in two column passes;
+        info() then reports gmax 8 / round_rows 8192), else 0 (dd_partitioner_pre_wide;
+        DD_PRE_WIDE=0|1 and DD_PRE_WIDE_MIN_ROWS at create time)."""
+        return int(lib().dd_partitioner_pre_wide(self.h))
+
     def k1_spec(self):
         """Key-signature code of the K1 hash/count kernel: 0 = generic run-time key loop,
         else kind(key 0) | kind(key 1) << 4 (dd_partitioner_k1_spec; DD_K1_SPEC=0 at

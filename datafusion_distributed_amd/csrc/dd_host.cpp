@@ -126,6 +126,13 @@ static int fixed_elem_size(int dtype) {
     }
 }
 
+/* Wide rounds (R = 8192) halve the block count of a batch, so they are
+ * the default only from DD_WIDE_MIN_ROWS rows up. All three eligible tiers (headline,
+ * dictkey, multikey) measured a step win beyond noise in both repeats at bench size, and
+ * the headline wins from 6 M rows up (profiles/r06_wide_rounds.txt); the threshold is held
+ * at 8 M so that plans of smaller batches stay what they were. */
+#define DD_WIDE_MIN_ROWS 8000000LL
+
 struct dd_partitioner {
     dd_batch_desc batch;
     dd_kargs ka;
@@ -143,6 +150,7 @@ struct dd_partitioner {
     uint32_t sP2 = 0;                  /* pre: imgb row stride (u16, even) */
     int pre_layout = 0; /* 0 not pre, 1 seg (k_hash_count_seg), 2 round (k_hash_count_round) */
     int pre_xcd = 0;    /* DD_PRE_XCD=1: k_scatter_pre walks rounds in XCD-contiguous order */
+    bool pre_wide = false; /* wide rounds: k_scatter_pre_wide (gmax 8, R = 8192) */
     int round_nr1 = 0, round_nr2 = 0; /* round layout: scan ranges (nr2 == 0: one level) */
     int k1_spec = 0; /* K1 key-signature code (DD_K1_CODE; 0 = generic dd_row_hash body) */
 
@@ -419,13 +427,50 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
                 int v = atoi(e);
                 if (v == 8 || v == 16) wpb = v;
             }
-            const int64_t R = (int64_t)pgmax * wpb * 64;
             const uint32_t sP2 = (n_partitions + 1) & ~1u;
-            const size_t lds = (size_t)R * rowb + 4 * (size_t)R +
-                               (size_t)wpb * (4 * (size_t)n_partitions + 2 * (size_t)sP2 +
-                                              2 * (size_t)n_partitions);
+            /* wide rounds (k_scatter_pre_wide): gmax 8 x wpb 16,
+             * R = 8192, round layout only, on the whitelisted shapes at P <= 128 (must
+             * mirror dd_launch_scatter_pre_wide). DD_PRE_WIDE=1 forces it on an eligible
+             * shape, 0 forbids it; unset, it is taken from DD_WIDE_MIN_ROWS rows up
+             * (DD_PRE_WIDE_MIN_ROWS overrides the threshold, for tests).
+             * DD_PRE_LAYOUT=seg always gets the narrow form. */
+            bool wide = false;
+            /* n < 2^29: the kernel addresses rows by 32-bit byte offsets (8 B elements) */
+            const bool wide_shape =
+                fixed_ok && n_partitions <= 128 && n < (1LL << 29) &&
+                (pre_is({8, 8, 8, 4}) || pre_is({4, 8, 8, 4}) || pre_is({8, 8, 8, 4, 4}));
+            const char *lay_env = getenv("DD_PRE_LAYOUT");
+            if (wide_shape && !(lay_env && strcmp(lay_env, "seg") == 0)) {
+                int64_t min_rows = DD_WIDE_MIN_ROWS;
+                if (const char *e = getenv("DD_PRE_WIDE_MIN_ROWS")) {
+                    const int64_t v = atoll(e);
+                    if (v >= 1) min_rows = v;
+                }
+                wide = n >= min_rows;
+                if (const char *e = getenv("DD_PRE_WIDE")) wide = atoi(e) == 1;
+            }
+            size_t lds_wide = 0;
+            if (wide) {
+                const size_t Rw = 8 * 16 * 64;
+                /* stage R x 16 B | gdelta u32[2][P] | pslot u8[R] | per-wave rf u16[sP2]
+                 * and ms u16[P] */
+                lds_wide = Rw * 16 + 8 * (size_t)n_partitions + Rw +
+                           16 * (2 * (size_t)sP2 + 2 * (size_t)n_partitions);
+                if (lds_wide > 163840) wide = false;
+            }
+            if (wide) {
+                pgmax = 8;
+                wpb = 16;
+            }
+            const int64_t R = (int64_t)pgmax * wpb * 64;
+            const size_t lds = wide ? lds_wide
+                                    : (size_t)R * rowb + 4 * (size_t)R +
+                                          (size_t)wpb * (4 * (size_t)n_partitions +
+                                                         2 * (size_t)sP2 +
+                                                         2 * (size_t)n_partitions);
             if (lds <= 163840) {
                 p->pre = true;
+                p->pre_wide = wide;
                 p->gmax = pgmax;
                 p->wpb = wpb;
                 p->lds_k3 = lds;
@@ -437,6 +482,9 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
                 p->rpb = 2; /* sweep (tools/sweep_pre.py): rpb2 K3 0.896 ms vs rpb1
                                0.953 / rpb4 0.924 / ceil(nrounds/2048)=8 1.079 on the
                                bench shape — small rpb beats in-block pipelining depth */
+                if (wide) p->rpb = 1; /* wide rounds, headline with the XCD order: rpb1 K3
+                                         0.72-0.77 ms vs rpb2 0.90-0.97 / rpb4 1.02; best
+                                         on dictkey and multikey too */
                 /* u8 pid array when P fits: 3 B/row less HBM write (K1) + read (K3);
                    DD_PID8=0 reverts */
                 if (n_partitions <= 256 &&
@@ -471,6 +519,9 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
                  * DD_PRE_XCD=0/1 overrides on any tier. */
                 p->pre_xcd = p->pre_layout == 2 && batch->n_cols == 4 &&
                              (n_partitions <= 128 || n_partitions > 256);
+                /* wide rounds: on at rpb 1 on all three tiers, the 5-column multikey
+                 * included (K3 0.81 against 0.95-1.06 ms with it off, §13.6) */
+                if (wide) p->pre_xcd = 1;
                 if (const char *e = getenv("DD_PRE_XCD")) p->pre_xcd = atoi(e) == 1;
                 /* round-granular scan: a thread walks <= span = 64 rounds; past 16*span
                  * ranges (> 65 k rounds) the range partials get a second level of
@@ -822,7 +873,12 @@ extern "C" dd_status dd_partitioner_run_phase2(dd_partitioner *p, void *stream) 
     if (!p) return set_err(DD_ERR_INVALID, "null partitioner");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipEventRecord(p->ev[4], s)); /* K3 start on the phase2 stream */
-    if (p->pre) {
+    if (p->pre_wide) {
+        const int64_t nblocks = (p->nrounds + p->rpb - 1) / p->rpb;
+        HIP_TRY(dd_launch_scatter_pre_wide(&p->ka, nblocks, p->nrounds, p->rpb, p->nparts,
+                                           p->nbits, p->pid, p->imgb, p->sP2, p->counts16,
+                                           p->rbase, p->pre_xcd, p->lds_k3, s));
+    } else if (p->pre) {
         const int64_t nblocks = (p->nrounds + p->rpb - 1) / p->rpb;
         HIP_TRY(dd_launch_scatter_pre(&p->ka, nblocks, p->nrounds, p->rpb, p->nparts,
                                       p->nbits, p->pid, p->gbase, p->imgb, p->sP2,
@@ -882,6 +938,10 @@ extern "C" int32_t dd_partitioner_pid_elem(const dd_partitioner *p) {
 
 extern "C" int32_t dd_partitioner_pre_layout(const dd_partitioner *p) {
     return p ? p->pre_layout : 0;
+}
+
+extern "C" int32_t dd_partitioner_pre_wide(const dd_partitioner *p) {
+    return p && p->pre_wide ? 1 : 0;
 }
 
 extern "C" int32_t dd_partitioner_k1_spec(const dd_partitioner *p) {

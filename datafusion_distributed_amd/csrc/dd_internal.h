@@ -173,6 +173,12 @@ hipError_t dd_launch_scatter_pre(const dd_kargs *a, int64_t nblocks, int64_t nro
                                  const uint16_t *imgb, uint32_t sP2, const uint16_t *segoff,
                                  const uint32_t *rbase, int layout, int xcd, int gmax,
                                  int wpb, size_t lds_bytes, hipStream_t s);
+hipError_t dd_launch_scatter_pre_wide(const dd_kargs *a, int64_t nblocks, int64_t nrounds,
+                                      int rpb, uint32_t nparts, int nbits,
+                                      const uint32_t *pid_in, const uint16_t *rofftab,
+                                      uint32_t sP2, const uint16_t *segoff,
+                                      const uint32_t *rbase, int xcd, size_t lds_bytes,
+                                      hipStream_t s);
 hipError_t dd_launch_hash_count_round(const dd_kargs *a, int k1_spec, int64_t nrounds,
                                       int64_t seg_rows, int wpb, uint32_t nparts,
                                       uint32_t sP2, uint32_t *pid_out, uint16_t *segoff,

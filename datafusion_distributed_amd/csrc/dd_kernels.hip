@@ -1631,6 +1631,346 @@ __global__ __launch_bounds__(W * WAVE) void k_scatter_pre(
     }
 }
 
+/* ---- wide rounds: k_scatter_pre's round layout at R = 8192 rows
+ * (16 waves x G = 8 row groups, SEG = 512), so every partition run of a round is twice as
+ * long as at R = 4096 (P = 128: 512 B for an 8-byte column). What makes it fit the same
+ * LDS budget:
+ *   - the round is staged in TWO column passes, each <= 16 B/row, through one R x 16 B
+ *     stage: columns [0, NA) in pass A, [NA, NC) in pass B. Pid, rank and image slot of
+ *     a row stay in registers across both; every column is still read once.
+ *   - the u32[R] dstg table is a u8[R] slot -> partition map (pslot) plus one per-block
+ *     gdelta[p] = rbase[r][p] - rofftab[r][p] (mod 2^32): a row at image slot i of
+ *     partition p goes to rbase + (i - roff) = gdelta[p] + i.
+ * LDS carve: stage R*16 | gdelta u32[2][P] | pslot u8[R] | per-wave rf u16[sP2] |
+ * per-wave ms u16[P]  (P = 128: 148,480 B). gdelta is double-buffered by round parity:
+ * wave 0 writes round r+1's row while other waves may still flush round r's pass B.
+ * Per round, with k_scatter_pre's hidden-load discipline (loads in inline asm, one
+ * counted wait per phase, flush stores never drained in-loop):
+ *   1. place pass A and pslot at slot = rf[pid] + rank                          barrier
+ *   2. issue this round's LB = G*(NC-NA) pass-B loads, flush pass A (LA = G*NA stores),
+ *      wait vmcnt(LA): the loads retired, the stores still in flight             barrier
+ *      (no pass-B write may land in the stage while a pass-A read is pending)
+ *   3. place pass B into the same stage                                          barrier
+ *   4. issue round r+1's G pid loads, LA pass-A loads and NB base loads, flush pass B
+ *      (LB stores), wait vmcnt(LB), write rf / gdelta, rank                      barrier
+ * Four barriers per 8192 rows, k_scatter_pre's rate. Ragged tail: inactive lanes load row
+ * end - 1 and place it at the unused slot R - 1, the flush clamps its slot to
+ * round_rows - 1. Loads address as scalar base + 32-bit byte offset (n_rows * 8 < 2^32,
+ * host-gated). One 1024-thread block per CU needs <= 128 VGPRs and NO spill: a spilled
+ * register of an in-flight asm load would be stored before it has arrived.
+ * Element sizes 4 and 8 only; P <= NBG * 64 <= 256 (pslot is a byte). Parity with the
+ * narrow form and the oracle: tests/test_gpu_wide_rounds.py. */
+template <int NA, int NBG, int... Es>
+__global__ __launch_bounds__(16 * WAVE) void k_scatter_pre_wide(
+    dd_kargs a, int64_t nrounds, int rpb, uint32_t nparts, int nbits,
+    const uint32_t *pid_in, const uint16_t *rofftab /* [nrounds][sP2] */, uint32_t sP2,
+    const uint16_t *segoff /* [nseg][sP2] */, const uint32_t *rbase /* [nrounds][sP2] */,
+    int xcd) {
+    constexpr int WPB = 16, GMAX = 8;
+    constexpr int BT = WPB * WAVE;
+    constexpr int R = GMAX * BT;
+    constexpr int SEG = R / WPB;
+    constexpr int NC = sizeof...(Es);
+    constexpr int EL[NC] = {Es...};
+    constexpr int LA = GMAX * NA, LB = GMAX * (NC - NA);
+    constexpr int NB = 3 * NBG;
+    constexpr int FLUSH_GROUP = 4; /* flush iterations scheduled together */
+    static_assert(NA > 0 && NA < NC, "two non-empty passes");
+    static_assert(LA <= 63 && LB <= 63, "vmcnt immediate is 6 bits");
+    static_assert(NBG <= 4, "pslot holds a partition in one byte");
+    struct slots { /* per pass (0 = A, 1 = B): register index and stage offset per column */
+        int idx[NC], off[NC];
+        int n8[2], n4[2], rowb[2];
+        constexpr slots() : idx{}, off{}, n8{}, n4{}, rowb{} {
+            for (int j = 0; j < NC; j++) {
+                const int ps = j >= NA;
+                idx[j] = (EL[j] == 8) ? n8[ps]++ : n4[ps]++;
+                off[j] = rowb[ps];
+                rowb[ps] += EL[j];
+            }
+        }
+        constexpr int n8max() const { return n8[0] > n8[1] ? n8[0] : n8[1]; }
+        constexpr int n4max() const { return n4[0] > n4[1] ? n4[0] : n4[1]; }
+        constexpr bool elems_ok() const {
+            for (int j = 0; j < NC; j++)
+                if (EL[j] != 4 && EL[j] != 8) return false;
+            return true;
+        }
+    };
+    constexpr slots S{};
+    static_assert(S.elems_ok(), "wide instantiations cover elem 4/8 only");
+    static_assert(S.rowb[0] <= 16 && S.rowb[1] <= 16, "a pass stages at most 16 B/row");
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char *ws = smem;
+    char *const stage0 = ws;
+    ws += (size_t)R * 16;
+    uint32_t *gdelta = (uint32_t *)ws;
+    ws += sizeof(uint32_t) * 2 * nparts;
+    uint8_t *pslot = (uint8_t *)ws;
+    ws += R;
+    uint16_t *rf_all = (uint16_t *)ws;
+    ws += sizeof(uint16_t) * WPB * sP2;
+    uint16_t *ms_all = (uint16_t *)ws;
+
+    const int tid = threadIdx.x;
+    const int wid = tid / WAVE;
+    const int lane = tid % WAVE;
+    uint16_t *rf = rf_all + (size_t)wid * sP2;
+    uint16_t *ms = ms_all + (size_t)wid * nparts;
+    const uint64_t lt = ((uint64_t)1 << lane) - 1;
+
+    const int64_t lb = xcd ? dd_xcd_block_map(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+    const int64_t r0 = lb * rpb;
+    const int64_t r1 = (r0 + rpb < nrounds) ? r0 + rpb : nrounds;
+    if (r0 >= nrounds || a.n_rows == 0) return;
+
+    uint32_t pidr[GMAX], rankr[GMAX], slotr[GMAX];
+    bool actr[GMAX];
+    /* [pass][column of that width][group]; every index is a compile-time constant */
+    uint64_t big[2][S.n8max() > 0 ? S.n8max() : 1][GMAX];
+    uint32_t sml[2][S.n4max() > 0 ? S.n4max() : 1][GMAX];
+    uint32_t rowc[GMAX];
+    uint32_t baser[NB]; /* NBG segoff u16, NBG rbase u32, NBG roff u16, at p = lane + k*64 */
+
+    /* clamped rows of this lane in round r; sets actr */
+    auto rows_of = [&](int64_t r) {
+        const int64_t rstart = r * R;
+        const int64_t rend = (rstart + R < a.n_rows) ? rstart + R : a.n_rows;
+        const int64_t segstart = rstart + (int64_t)wid * SEG;
+#pragma unroll
+        for (int g = 0; g < GMAX; g++) {
+            const int64_t row = segstart + g * WAVE + lane;
+            actr[g] = row < rend;
+            rowc[g] = (uint32_t)(actr[g] ? row : rend - 1); /* always issue (counts) */
+        }
+    };
+
+    /* column loads of one pass: exactly G loads per column, in column order */
+    auto load_pass = [&](auto psc) {
+        constexpr int PS = psc.value, J0 = PS ? NA : 0, J1 = PS ? NC : NA;
+        /* named captures: asm operands alone do not make a generic lambda nested in a
+         * generic lambda capture them */
+        hl_for<J0, J1>([&a, &big, &sml, &rowc](auto jc) {
+            constexpr int J = jc.value;
+            const void *base = a.cols[J].data;
+#pragma unroll
+            for (int g = 0; g < GMAX; g++) {
+                /* scalar base + 32-bit byte offset: one address VGPR per load, shared
+                 * by the columns of one width (the host keeps n_rows * 8 < 2^32) */
+                if constexpr (EL[J] == 8)
+                    asm volatile("global_load_dwordx2 %0, %1, %2"
+                                 : "=v"(big[PS][S.idx[J]][g])
+                                 : "v"(rowc[g] << 3), "s"(base));
+                else
+                    asm volatile("global_load_dword %0, %1, %2"
+                                 : "=v"(sml[PS][S.idx[J]][g])
+                                 : "v"(rowc[g] << 2), "s"(base));
+            }
+        });
+    };
+
+    auto wait_pass = [&](auto cnt, auto psc) {
+        constexpr int PS = psc.value, J0 = PS ? NA : 0, J1 = PS ? NC : NA;
+        constexpr int CNT = cnt.value;
+        hl_for<J0, J1>([&big, &sml](auto jc) {
+            constexpr int J = jc.value;
+#pragma unroll
+            for (int g = 0; g < GMAX; g++) {
+                if constexpr (EL[J] == 8) hl_tie_wait<CNT>(big[PS][S.idx[J]][g]);
+                else hl_tie_wait<CNT>(sml[PS][S.idx[J]][g]);
+            }
+        });
+    };
+
+    /* round r's pid loads, pass-A column loads and base-row loads: G + LA + NB loads */
+    auto preload = [&](int64_t r) {
+        rows_of(r);
+        if (a.pid8) { /* uniform branch; exactly G pid loads issue either way */
+#pragma unroll
+            for (int g = 0; g < GMAX; g++)
+                asm volatile("global_load_ubyte %0, %1, %2"
+                             : "=v"(pidr[g])
+                             : "v"(rowc[g]), "s"(pid_in));
+        } else {
+#pragma unroll
+            for (int g = 0; g < GMAX; g++)
+                asm volatile("global_load_dword %0, %1, %2"
+                             : "=v"(pidr[g])
+                             : "v"(rowc[g] << 2), "s"(pid_in));
+        }
+        load_pass(std::integral_constant<int, 0>{});
+        /* my segment's segoff row + the round's rbase and roff rows (the last two are the
+         * same for every wave and L2-hot) */
+        const int64_t seg = r * WPB + wid;
+        const uint16_t *srow = segoff + (size_t)seg * sP2;
+        const uint32_t *brow = rbase + (size_t)r * sP2;
+        const uint16_t *irow = rofftab + (size_t)r * sP2;
+        uint32_t idxk[NBG];
+#pragma unroll
+        for (int k = 0; k < NBG; k++) {
+            idxk[k] = (uint32_t)lane + k * WAVE;
+            if (idxk[k] >= nparts) idxk[k] = nparts - 1; /* redundant re-load */
+        }
+#pragma unroll
+        for (int k = 0; k < NBG; k++)
+            asm volatile("global_load_ushort %0, %1, off"
+                         : "=v"(baser[k])
+                         : "v"(srow + idxk[k]));
+#pragma unroll
+        for (int k = 0; k < NBG; k++) HL_LD32(baser[NBG + k], brow + idxk[k]);
+#pragma unroll
+        for (int k = 0; k < NBG; k++)
+            asm volatile("global_load_ushort %0, %1, off"
+                         : "=v"(baser[2 * NBG + k])
+                         : "v"(irow + idxk[k]));
+    };
+
+    auto wait_preload = [&](auto cnt) { /* pid + pass-A columns + bases retired */
+#pragma unroll
+        for (int g = 0; g < GMAX; g++) hl_tie_wait<cnt.value>(pidr[g]);
+        wait_pass(cnt, std::integral_constant<int, 0>{});
+#pragma unroll
+        for (int k = 0; k < NB; k++) hl_tie_wait<cnt.value>(baser[k]);
+    };
+
+    /* rf[p] = my segment's first image slot (wave-private); wave 0 also writes the
+     * block's gdelta row of that round into the buffer of its parity */
+    auto write_base_rows = [&](uint32_t *gd) {
+#pragma unroll
+        for (int k = 0; k < NBG; k++) {
+            uint32_t idx = (uint32_t)lane + k * WAVE;
+            if (idx < nparts) {
+                rf[idx] = (uint16_t)(baser[2 * NBG + k] + baser[k]);
+                if (wid == 0) gd[idx] = baser[NBG + k] - baser[2 * NBG + k];
+            }
+        }
+    };
+
+    auto rank = [&]() {
+        for (uint32_t p = lane; p < nparts; p += WAVE) ms[p] = 0;
+#pragma unroll
+        for (int g = 0; g < GMAX; g++) {
+            const bool active = actr[g];
+            const uint32_t pid = pidr[g];
+            uint64_t act = __ballot(active);
+            uint32_t rk = 0;
+            if (active) {
+                uint64_t eq = dd_eq_mask(pid, act, nbits);
+                int leader = __ffsll((unsigned long long)eq) - 1;
+                uint32_t base = 0;
+                if (lane == leader) {
+                    base = ms[pid];
+                    ms[pid] = (uint16_t)(base + (uint32_t)__popcll((unsigned long long)eq));
+                }
+                base = (uint32_t)__shfl((int)base, leader);
+                rk = base + (uint32_t)__popcll((unsigned long long)(eq & lt));
+            }
+            rankr[g] = rk;
+        }
+    };
+
+    auto place_pass = [&](auto psc) {
+        constexpr int PS = psc.value, J0 = PS ? NA : 0, J1 = PS ? NC : NA;
+        /* branch-free: an inactive lane (ragged tail round only, so round_rows < R)
+         * writes slot R - 1, which no row of that round owns and the flush never reads */
+#pragma unroll
+        for (int g = 0; g < GMAX; g++) {
+            uint32_t slot;
+            if constexpr (PS == 0) {
+                slot = actr[g] ? (uint32_t)rf[pidr[g]] + rankr[g] : (uint32_t)(R - 1);
+                slotr[g] = slot;
+                /* opaque: the slot itself lives on to pass B, not its scaled copies */
+                asm volatile("" : "+v"(slotr[g]));
+                pslot[slot] = (uint8_t)pidr[g];
+            } else {
+                slot = slotr[g];
+            }
+            hl_for<J0, J1>([&](auto jc) {
+                constexpr int J = jc.value;
+                char *stage = stage0 + (size_t)R * S.off[J];
+                if constexpr (EL[J] == 8) ((uint64_t *)stage)[slot] = big[PS][S.idx[J]][g];
+                else ((uint32_t *)stage)[slot] = sml[PS][S.idx[J]][g];
+            });
+        }
+    };
+
+    /* flush padded to GMAX iterations (clamped rewrite is idempotent): exactly G stores
+     * per column of the pass; plain (cached) stores as in k_scatter_pre */
+    auto flush_pass = [&](auto psc, int round_rows, const uint32_t *gd) {
+        constexpr int J0 = psc.value ? NA : 0, J1 = psc.value ? NC : NA;
+        /* opaque: otherwise the two flushes of a round share their LDS addresses, which
+         * then stay live (24+ VGPRs) across the phases between them */
+        int tido = tid;
+        asm volatile("" : "+v"(tido));
+#pragma unroll
+        for (int u = 0; u < GMAX; u++) {
+            const int i = tido + u * BT;
+            const int ic = (i < round_rows) ? i : (round_rows - 1);
+            const uint64_t dst = (uint32_t)(gd[pslot[ic]] + (uint32_t)ic);
+            hl_for<J0, J1>([&](auto jc) {
+                constexpr int J = jc.value;
+                void *out = a.cols[J].out_data;
+                const char *stage = stage0 + (size_t)R * S.off[J];
+                if constexpr (EL[J] == 8)
+                    ((uint64_t *)out)[dst] = ((const uint64_t *)stage)[ic];
+                else
+                    ((uint32_t *)out)[dst] = ((const uint32_t *)stage)[ic];
+            });
+            /* the flush runs with the next phase's loads in flight (up to 46 result
+             * registers): keep the scheduler from hoisting all G iterations' LDS reads
+             * and store addresses above them, which spills. A spill of an in-flight
+             * asm load's register would also store it before it has arrived. */
+            if ((u & (FLUSH_GROUP - 1)) == FLUSH_GROUP - 1) __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+
+    constexpr std::integral_constant<int, 0> PA{};
+    constexpr std::integral_constant<int, 1> PB{};
+
+    /* prologue: first round's loads, base rows, rank */
+    preload(r0);
+    wait_preload(std::integral_constant<int, 0>{});
+    write_base_rows(gdelta);
+    rank();
+    __syncthreads();
+
+    for (int64_t r = r0; r < r1; r++) {
+        const int64_t rstart = r * R;
+        const int round_rows =
+            (int)(((rstart + R < a.n_rows) ? rstart + R : a.n_rows) - rstart);
+        const uint32_t *gd = gdelta + (size_t)((r - r0) & 1) * nparts;
+        uint32_t *gdn = gdelta + (size_t)((r - r0 + 1) & 1) * nparts;
+
+        /* 1. place pass A: everything it needs was waited on before the preceding
+         * barrier; the only VMEM in flight is the previous round's pass-B stores */
+        place_pass(PA);
+        __syncthreads();
+
+        /* 2. pass-B loads of this round behind the pass-A flush */
+        rows_of(r);
+        load_pass(PB);
+        flush_pass(PA, round_rows, gd);
+        wait_pass(std::integral_constant<int, LA>{}, PB);
+        __syncthreads();
+
+        /* 3. place pass B into the same stage */
+        place_pass(PB);
+        __syncthreads();
+
+        /* 4. next round's loads behind the pass-B flush */
+        const bool more = r + 1 < r1;
+        if (more) preload(r + 1);
+        flush_pass(PB, round_rows, gd);
+        if (more) {
+            wait_preload(std::integral_constant<int, LB>{});
+            write_base_rows(gdn);
+            rank();
+        }
+        __syncthreads();
+    }
+}
+
 /* K1 for the pre path: per-SEGMENT histograms (segment = one wave's SEG contiguous rows
  * of a globally-aligned round). 4 segments per 256-thread block; per-wave LDS hist.
  * Fuses the first scan pass: each wave atomicAdds its histogram into its range row of
@@ -2631,6 +2971,44 @@ hipError_t dd_launch_scatter_pre(const dd_kargs *a, int64_t nblocks, int64_t nro
     DD_PRE(2, 8, 4, 8, 8, 8, 4, 4)
 #undef DD_PRE
 #undef DD_PREW
+    return hipErrorInvalidValue;
+}
+
+/* wide rounds (k_scatter_pre_wide: gmax 8, wpb 16, round layout). The host whitelists the
+ * exact shapes; must mirror dd_partitioner_create's wide gate. */
+hipError_t dd_launch_scatter_pre_wide(const dd_kargs *a, int64_t nblocks, int64_t nrounds,
+                                      int rpb, uint32_t nparts, int nbits,
+                                      const uint32_t *pid_in, const uint16_t *rofftab,
+                                      uint32_t sP2, const uint16_t *segoff,
+                                      const uint32_t *rbase, int xcd, size_t lds_bytes,
+                                      hipStream_t s) {
+    dim3 grid((unsigned)nblocks);
+    const int n = a->n_cols;
+    auto el = [&](int c) { return (int)a->cols[c].elem; };
+#define DD_PREWIDE(NA_, NBG_, ...)                                                           \
+    {                                                                                        \
+        const int want[] = {__VA_ARGS__};                                                    \
+        const int wn = (int)(sizeof(want) / sizeof(want[0]));                                \
+        bool m = (n == wn && nparts <= (uint32_t)(NBG_ * WAVE));                             \
+        for (int c = 0; c < wn && m; c++) m = el(c) == want[c];                              \
+        if (m) {                                                                             \
+            auto kfn = k_scatter_pre_wide<NA_, NBG_, __VA_ARGS__>;                           \
+            if (lds_bytes > 65536) {                                                         \
+                hipError_t e = hipFuncSetAttribute(                                          \
+                    (const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,           \
+                    (int)lds_bytes);                                                         \
+                if (e != hipSuccess) return e;                                               \
+            }                                                                                \
+            hipLaunchKernelGGL(kfn, grid, dim3(16 * WAVE), lds_bytes, s, *a, nrounds, rpb,   \
+                               nparts, nbits, pid_in, rofftab, sP2, segoff, rbase, xcd);     \
+            return hipGetLastError();                                                        \
+        }                                                                                    \
+    }
+    /* P <= 128 (NBG = 2); the first NA columns go in pass A */
+    DD_PREWIDE(2, 2, 8, 8, 8, 4)    /* headline  {8,8 | 8,4} */
+    DD_PREWIDE(2, 2, 4, 8, 8, 4)    /* dictkey   {4,8 | 8,4} */
+    DD_PREWIDE(2, 2, 8, 8, 8, 4, 4) /* multikey  {8,8 | 8,4,4} */
+#undef DD_PREWIDE
     return hipErrorInvalidValue;
 }
 

@@ -148,6 +148,13 @@ dd_status dd_partitioner_get_info(const dd_partitioner *p, dd_partitioner_info *
  * segment (k_hash_count_seg + segment-granular scan), 2 = per round (k_hash_count_round +
  * round-granular scan). Kept out of dd_partitioner_info, whose size is part of the ABI. */
 int32_t dd_partitioner_pre_layout(const dd_partitioner *p);
+/* 1 when the pre path scatters in wide rounds (8192 rows per round staged in two column
+ * passes, k_scatter_pre_wide; dd_partitioner_info then reports gmax 8 and round_rows 8192),
+ * else 0. Eligible: round layout, P <= 128, no validity, element sizes (8,8,8,4),
+ * (4,8,8,4) or (8,8,8,4,4). DD_PRE_WIDE=1 forces it on an eligible shape and 0 forbids it;
+ * unset, it is taken from 8,000,000 rows up (DD_PRE_WIDE_MIN_ROWS overrides the
+ * threshold) and below 2^29 rows. Results do not depend on it. */
+int32_t dd_partitioner_pre_wide(const dd_partitioner *p);
 /* the compile-time key signature the K1 hash/count kernel runs with: 0 = the generic
  * run-time key loop; otherwise kind(key 0) | kind(key 1) << 4 with kinds 1 u8/bool, 2 i16,
  * 3 i32, 4 i64, 5 f32, 6 f64, 7 dict32. Chosen at create time for one non-nullable key of

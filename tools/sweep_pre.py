@@ -39,12 +39,22 @@ CONFIGS = [
     ("plain", {"DD_K3_PRE": "0", "DD_K3_HL": "0"}),
     ("spec", {}),                       # the default: K1 with its compile-time key signature
     ("generic", {"DD_K1_SPEC": "0"}),   # K1 with the run-time key loop
+    ("narrow", {"DD_PRE_WIDE": "0"}),   # 4096-row rounds
+    ("wide", {"DD_PRE_WIDE": "1"}),     # 8192-row rounds in two column passes
+    ("wide-rpb1", {"DD_PRE_WIDE": "1", "DD_PRE_RPB": "1"}),
+    ("wide-rpb2", {"DD_PRE_WIDE": "1", "DD_PRE_RPB": "2"}),
+    ("wide-rpb1-xcd0", {"DD_PRE_WIDE": "1", "DD_PRE_RPB": "1", "DD_PRE_XCD": "0"}),
+    ("wide-rpb1-xcd1", {"DD_PRE_WIDE": "1", "DD_PRE_RPB": "1", "DD_PRE_XCD": "1"}),
+    ("wide-rpb4", {"DD_PRE_WIDE": "1", "DD_PRE_RPB": "4"}),
+    ("wide-xcd0", {"DD_PRE_WIDE": "1", "DD_PRE_XCD": "0"}),
+    ("wide-xcd1", {"DD_PRE_WIDE": "1", "DD_PRE_XCD": "1"}),
 ]
 if len(sys.argv) > 4:
     CONFIGS = [c for c in CONFIGS if c[0] in sys.argv[4].split(",")]
 
 KNOBS = ["DD_K3_PRE", "DD_K3_HL", "DD_PID8", "DD_PRE_NT", "DD_PRE_RPB", "DD_PRE_GMAX",
-         "DD_PRE_WPB", "DD_PRE_LAYOUT", "DD_PRE_XCD", "DD_K1_SPEC"]
+         "DD_PRE_WPB", "DD_PRE_LAYOUT", "DD_PRE_XCD", "DD_K1_SPEC", "DD_PRE_WIDE",
+         "DD_PRE_WIDE_MIN_ROWS"]
 
 
 def main():
@@ -59,7 +69,8 @@ def main():
         part = api.Partitioner(batch, key_idx, P)
         parts.append((name, part))
         print(name, "plan", json.dumps({**part.info(), "pre_layout": part.pre_layout(),
-                                        "k1_spec": part.k1_spec()}),
+                                        "k1_spec": part.k1_spec(),
+                                        "pre_wide": part.pre_wide()}),
               flush=True)
     samples = {name: [] for name, _ in CONFIGS}
     for r in range(REPS + 2):
