@@ -124,6 +124,18 @@ def lib():
         L.dd_exchanged_dict_n.restype = ctypes.c_int64
         L.dd_exchanged_dict_offsets.restype = ctypes.c_void_p
         L.dd_exchanged_dict_bytes.restype = ctypes.c_void_p
+        L.dd_view_ingest_offsets.restype = ctypes.c_void_p
+        L.dd_view_ingest_bytes.restype = ctypes.c_void_p
+        L.dd_view_ingest_data_len.restype = ctypes.c_int64
+        L.dd_view_ingest_tier.restype = ctypes.c_int32
+        L.dd_view_ingest_destroy.restype = None
+        L.dd_view_ingest_destroy.argtypes = [ctypes.c_void_p]
+        L.dd_view_tile_rows.restype = ctypes.c_int32
+        L.dd_view_image_bytes.restype = ctypes.c_int32
+        L.dd_view_emit_views.restype = ctypes.c_void_p
+        L.dd_view_emit_bytes.restype = ctypes.c_void_p
+        L.dd_view_emit_destroy.restype = None
+        L.dd_view_emit_destroy.argtypes = [ctypes.c_void_p]
         _lib = L
     return _lib
 
@@ -169,16 +181,24 @@ class DeviceBatch:
 
     def __init__(self, cols):
         self.cols = cols
-        self.n_rows = (len(cols[0]["offsets"]) - 1 if cols[0]["dtype"] == "utf8"
-                       else len(cols[0]["data"]))
+        if cols[0]["dtype"] == "utf8":
+            self.n_rows = len(cols[0]["offsets"]) - 1
+        elif cols[0]["dtype"] == "utf8view":
+            self.n_rows = len(np.asarray(cols[0]["views"], dtype=np.uint8).reshape(-1, 16))
+        else:
+            self.n_rows = len(cols[0]["data"])
         self._bufs = []
         self._host_refs = (None, None)
         self._utf8_maxlen = {}  # col -> longest string uploaded at construction
+        self._ingests = {}  # col -> ViewIngest owning a utf8view column's offsets + bytes
         self.desc = BatchDesc()
         self.desc.n_rows = self.n_rows
         self.desc.n_cols = len(cols)
         for i, col in enumerate(cols):
             cd = self.desc.cols[i]
+            if col["dtype"] == "utf8view":
+                self._ingest_views(i, col, cd)
+                continue
             cd.dtype = DTYPE_CODE[col["dtype"]]
             if col["dtype"] == "utf8":
                 data = np.ascontiguousarray(col["data"], dtype=np.uint8)
@@ -200,6 +220,31 @@ class DeviceBatch:
                 cd.dict_offsets = self._up(np.ascontiguousarray(col["dict_offsets"], np.int32))
                 cd.dict_n = len(col["dict_offsets"]) - 1
 
+    def _ingest_views(self, i, col, cd):
+        """Upload a {"dtype": "utf8view", "views", "bufs", "valid"} column, run the view
+        ingest on it and describe the result to C as an ordinary UTF8 column."""
+        views = np.ascontiguousarray(col["views"], dtype=np.uint8).reshape(-1, 16)
+        if len(views) != self.n_rows:
+            raise ValueError(f"column {i} has {len(views)} views, batch has {self.n_rows} rows")
+        valid = col.get("valid")
+        vp = None
+        lens = views.view(np.int32).reshape(-1, 4)[:, 0]
+        if valid is not None:
+            valid = np.ascontiguousarray(valid, np.uint8)
+            vp = self._up(valid)
+            lens = lens[valid != 0]
+        bufs = [np.ascontiguousarray(b, dtype=np.uint8) for b in col.get("bufs", [])]
+        ing = ViewIngest(self._up(views), vp, self.n_rows, [self._up(b) for b in bufs],
+                         [int(b.nbytes) for b in bufs])
+        self._ingests[i] = ing
+        cd.dtype = DTYPE_CODE["utf8"]
+        cd.data = ing.bytes_ptr
+        cd.offsets = ing.offsets_ptr
+        cd.data_len = ing.data_len
+        if vp is not None:
+            cd.validity = vp
+        self._utf8_maxlen[i] = int(lens.max()) if len(lens) else 0
+
     @classmethod
     def from_device(cls, view_cols, n_rows):
         """Non-owning device-view batch: each col gives raw device pointers
@@ -212,6 +257,7 @@ class DeviceBatch:
         self._bufs = []
         self._host_refs = (None, None)
         self._utf8_maxlen = {}
+        self._ingests = {}
         self.desc = BatchDesc()
         self.desc.n_rows = n_rows
         self.desc.n_cols = len(view_cols)
@@ -241,6 +287,9 @@ class DeviceBatch:
         (dd_shuffle.h, above dd_partitioner_run) and return the (device pointer, host
         array) copies a refill would make. Raises ValueError on the first mismatch;
         touches neither the device nor the library."""
+        if self._ingests:
+            raise ValueError(f"refill: column {min(self._ingests)} is a utf8view column "
+                             "(re-ingest into a live batch is not supported)")
         if len(cols) != self.desc.n_cols:
             raise ValueError(f"refill: {len(cols)} columns, batch has {self.desc.n_cols}")
         n = self.n_rows
@@ -328,6 +377,9 @@ class DeviceBatch:
         self.cols = cols
 
     def free(self):
+        for ing in self._ingests.values():
+            ing.destroy()
+        self._ingests = {}
         for b in self._bufs:
             lib().dd_dev_free(b)
         self._bufs = []
@@ -438,8 +490,11 @@ class Partitioner:
         col = self.batch.cols[i]
         n = self.batch.n_rows
         res = {"dtype": col["dtype"]}
-        if col["dtype"] == "utf8":
-            dl = int(np.asarray(col["data"], dtype=np.uint8).nbytes)
+        if col["dtype"] in ("utf8", "utf8view"):
+            # a view column was ingested to utf8: it comes out in the usual utf8 shape
+            res["dtype"] = "utf8"
+            dl = (self.batch._ingests[i].data_len if col["dtype"] == "utf8view"
+                  else int(np.asarray(col["data"], dtype=np.uint8).nbytes))
             res["data"] = _d2h(lib().dd_partitioner_col_data(self.h, i), dl, np.uint8)
             res["lengths"] = _d2h(lib().dd_partitioner_col_lengths(self.h, i), n * 4,
                                   np.uint32)
@@ -506,6 +561,142 @@ class DictGC:
     def destroy(self):
         if self.h:
             lib().dd_dict_gc_destroy(self.h)
+            self.h = None
+
+
+class ViewIngest:
+    """dd_view_ingest_*: Arrow views + their data buffers -> a dense utf8 column (i32
+    offsets + bytes) on the device. Takes raw device pointers; from_host
+    uploads numpy arrays first and owns those uploads."""
+
+    def __init__(self, views_ptr, valid_ptr, n_rows, buf_ptrs, buf_lens, stream=None):
+        nb = len(buf_ptrs)
+        ptrs = (ctypes.c_void_p * max(nb, 1))(*buf_ptrs)
+        lens = (ctypes.c_int64 * max(nb, 1))(*buf_lens)
+        self.n_rows = n_rows
+        self._owned = []
+        self.h = ctypes.c_void_p()
+        _check(lib().dd_view_ingest_run(
+            ctypes.c_void_p(views_ptr), ctypes.c_void_p(valid_ptr), ctypes.c_int64(n_rows),
+            ptrs, lens, ctypes.c_int32(nb), _stream_arg(stream), ctypes.byref(self.h)))
+        self.data_len = int(lib().dd_view_ingest_data_len(self.h))
+        self.offsets_ptr = lib().dd_view_ingest_offsets(self.h)
+        self.bytes_ptr = lib().dd_view_ingest_bytes(self.h)
+
+    @classmethod
+    def from_host(cls, views, valid, bufs, buf_lens=None, stream=None):
+        """Upload views u8[n,16], valid u8[n] or None and the data buffers, then ingest.
+        buf_lens overrides the lengths stated to the library (default: the arrays')."""
+        owned = []
+
+        def up(arr):
+            arr = np.ascontiguousarray(arr, dtype=np.uint8)
+            p = _dev_alloc(arr.nbytes)
+            if arr.nbytes:
+                _h2d(p, arr)
+            owned.append(p)
+            return p.value
+
+        try:
+            views = np.ascontiguousarray(views, dtype=np.uint8).reshape(-1, 16)
+            vp = up(views)
+            validp = up(valid) if valid is not None else None
+            ptrs = [up(b) for b in bufs]
+            if buf_lens is None:
+                buf_lens = [int(np.asarray(b).nbytes) for b in bufs]
+            self = cls(vp, validp, len(views), ptrs, buf_lens, stream)
+        except Exception:
+            for p in owned:
+                lib().dd_dev_free(p)
+            raise
+        self._owned = owned
+        return self
+
+    def tier(self):
+        """1 = LDS-staged copy (DD_VIEW_LDS=1), 0 = direct (the default, or every tile
+        outgrew the image)."""
+        return int(lib().dd_view_ingest_tier(self.h))
+
+    def offsets(self):
+        return _d2h(self.offsets_ptr, (self.n_rows + 1) * 4, np.int32)
+
+    def bytes(self):
+        return (_d2h(self.bytes_ptr, self.data_len, np.uint8) if self.data_len
+                else np.zeros(0, dtype=np.uint8))
+
+    def kernel_ms(self):
+        """[length pass, scan, copy] hipEvent durations of the run, in ms."""
+        out = (ctypes.c_float * 3)()
+        _check(lib().dd_view_ingest_kernel_ms(self.h, out))
+        return list(out)
+
+    def destroy(self):
+        if self.h:
+            lib().dd_view_ingest_destroy(self.h)
+            self.h = None
+        for p in self._owned:
+            lib().dd_dev_free(p)
+        self._owned = []
+
+
+def view_tile_rows():
+    """Rows per copy tile of the view kernels (dd_view_tile_rows; needs no device)."""
+    return int(lib().dd_view_tile_rows())
+
+
+def view_image_bytes():
+    """Bytes of the LDS image of the staged copy tier (dd_view_image_bytes)."""
+    return int(lib().dd_view_image_bytes())
+
+
+class ViewEmit:
+    """dd_view_emit_*: one utf8 column of a run Partitioner as compact per-window Arrow
+    view arrays: 16-byte views, partition-major, plus one data buffer per
+    window holding only the long values. The partitioner's own output is untouched and
+    must outlive this object."""
+
+    def __init__(self, part: Partitioner, col: int, n_windows: int, stream=None):
+        self.part = part
+        self.col = col
+        self.n_windows = n_windows
+        self.h = ctypes.c_void_p()
+        _check(lib().dd_view_emit_run(part.h, col, ctypes.c_uint32(n_windows),
+                                      _stream_arg(stream), ctypes.byref(self.h)))
+        self._counts = None
+
+    def counts(self):
+        """long_byte_off: host prefix sums i64[n_windows+1] of the windows' buffers."""
+        if self._counts is None:
+            b = np.empty(self.n_windows + 1, dtype=np.int64)
+            _check(lib().dd_view_emit_counts(
+                self.h, b.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            self._counts = b
+        return self._counts
+
+    def views(self):
+        """Download the u8[n_rows, 16] views."""
+        n = self.part.batch.n_rows
+        if n == 0:
+            return np.zeros((0, 16), dtype=np.uint8)
+        return _d2h(lib().dd_view_emit_views(self.h), n * 16, np.uint8).reshape(n, 16)
+
+    def window_bytes(self, w):
+        """Download window w's data buffer."""
+        b = self.counts()
+        nb = int(b[w + 1] - b[w])
+        if nb == 0:
+            return np.zeros(0, dtype=np.uint8)
+        return _d2h(lib().dd_view_emit_bytes(self.h) + int(b[w]), nb, np.uint8)
+
+    def kernel_ms(self):
+        """[scan, build, copy] hipEvent durations of the run, in ms."""
+        out = (ctypes.c_float * 3)()
+        _check(lib().dd_view_emit_kernel_ms(self.h, out))
+        return list(out)
+
+    def destroy(self):
+        if self.h:
+            lib().dd_view_emit_destroy(self.h)
             self.h = None
 
 
@@ -631,7 +822,7 @@ class Exchanged:
     def col_data(self, i):
         col = self.part.batch.cols[i]
         n = self.total_rows
-        if col["dtype"] == "utf8":
+        if col["dtype"] in ("utf8", "utf8view"):
             total_b = int(self.byte_counts(i).sum())
             data = _d2h(lib().dd_exchanged_col_data(self.h, i), total_b, np.uint8)
             lens = _d2h(lib().dd_exchanged_col_lengths(self.h, i), n * 4, np.uint32)

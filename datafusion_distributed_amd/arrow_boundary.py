@@ -38,16 +38,28 @@ def _utf8_values(pa, offsets, data):
         len(doff) - 1, pa.py_buffer(doff.tobytes()), pa.py_buffer(dbuf.tobytes()), None)
 
 
-def partition_batches(part, lo, hi, batch_size=8192, gc=None):
+def partition_batches(part, lo, hi, batch_size=8192, gc=None, views=None):
     """Arrow RecordBatches for partitions [lo, hi) of a run Partitioner (downloads the
     partition-major buffers once and slices views). Yields (partition, RecordBatch).
 
     gc: optional {col: DictGC} run with n_windows == part.nparts (one dictionary per
     partition, the reference's per-batch granularity, worker_service.rs:363-433): those
     columns' DictionaryArrays use the remapped indices and the partition's compacted
-    dictionary. Without it every batch carries the full input dictionary."""
+    dictionary. Without it every batch carries the full input dictionary.
+
+    views: optional {col: ViewEmit} run with n_windows == part.nparts: those utf8 columns
+    come out as pa.string_view() arrays over the partition's compact data buffer (every
+    batch of a partition shares that one buffer: slicing at batch_size copies nothing).
+    Without it they are pa.string() arrays, as before."""
     pa = _arrow()
     gc = gc or {}
+    views = views or {}
+    ve_views, ve_bufs = {}, {}
+    for i, e in views.items():
+        if e.n_windows != part.nparts or e.part is not part or e.col != i:
+            raise ValueError("partition_batches: ViewEmit must be run on this partitioner "
+                             "and column with n_windows == part.nparts")
+        ve_views[i] = e.views()
     gc_idx = {}
     for i, g in gc.items():
         if g.n_windows != part.nparts or g.part is not part:
@@ -63,7 +75,9 @@ def partition_batches(part, lo, hi, batch_size=8192, gc=None):
     valid = {}
     for i, c in enumerate(cols_meta):
         out = part.col_out(i)
-        if c["dtype"] == "utf8":
+        if i in views:
+            pass  # the emit object holds this column's views and buffers
+        elif c["dtype"] in ("utf8", "utf8view"):
             lens[i] = out["lengths"]
             var_bytes[i] = out["data"]
             var_boff[i] = part.byte_offsets(i)
@@ -85,7 +99,15 @@ def partition_batches(part, lo, hi, batch_size=8192, gc=None):
                 mask = None
                 if i in valid:
                     mask = ~_validity_mask(valid[i][b0:b1])
-                if c["dtype"] == "utf8":
+                if i in views:
+                    if ve_bufs.get(i, (None,))[0] != p:  # one partition's buffer at a time
+                        ve_bufs[i] = (p, pa.py_buffer(views[i].window_bytes(p).tobytes()))
+                    arr = pa.Array.from_buffers(
+                        pa.string_view(), b1 - b0,
+                        [pa.py_buffer(np.packbits(~mask, bitorder="little").tobytes())
+                         if mask is not None else None,
+                         pa.py_buffer(ve_views[i][b0:b1].tobytes()), ve_bufs[i][1]])
+                elif c["dtype"] in ("utf8", "utf8view"):
                     seg_lens = lens[i][b0:b1].astype(np.int64)
                     start = int(var_boff[i][p]) + int(
                         lens[i][r0:b0].astype(np.int64).sum())

@@ -1495,6 +1495,262 @@ extern "C" dd_status dd_dict_gc_kernel_ms(const dd_dict_gc *g, float out_ms[4]) 
     return DD_OK;
 }
 
+/* ---------------- view columns (dd_view_ingest / dd_view_emit; kernels in dd_views.hip) ---
+ * Device statement of the view half of garbage_collect_arrays
+ * (src/protocol/grpc/worker_service.rs:408-433). DESIGN.md §15. */
+
+/* Copy tier knob, read per call: DD_VIEW_LDS=1 takes the LDS-staged tier, 0 or unset the
+ * direct tier. Direct is the default because it measured 1.5-1.6x faster on the
+ * clickbench_userid shape (profiles/r07_views.json). */
+static int dd_view_lds_enabled(void) {
+    const char *e = getenv("DD_VIEW_LDS");
+    return e && atoi(e) != 0;
+}
+
+extern "C" int32_t dd_view_tile_rows(void) { return DD_VW_TILE_ROWS; }
+extern "C" int32_t dd_view_image_bytes(void) { return DD_VW_IMAGE_BYTES; }
+
+struct dd_view_ingest {
+    int64_t n_rows = 0, n_tiles = 0, data_len = 0;
+    int32_t tier = 0;
+    int32_t *offs = nullptr;   /* [n_tiles * DD_VW_TILE_ROWS + 4]; offsets[n_rows+1] */
+    uint8_t *bytes = nullptr;
+    uint64_t *tsum = nullptr;  /* [n_tiles] then the scan [n_tiles+1] then meta[2] */
+    uint32_t *flag = nullptr;
+    void *tab = nullptr;       /* device: n_bufs pointers then n_bufs i64 lengths */
+    hipEvent_t ev[5] = {};     /* len: 0-1, scan (+add): 1-2, copy: 3-4 */
+    bool copied = false;
+    ~dd_view_ingest() {
+        (void)hipFree(offs);
+        (void)hipFree(bytes);
+        (void)hipFree(tsum);
+        (void)hipFree(flag);
+        (void)hipFree(tab);
+        for (auto &e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+extern "C" dd_status dd_view_ingest_run(const void *views, const uint8_t *validity,
+                                        int64_t n_rows, const void *const *data_bufs,
+                                        const int64_t *data_buf_lens, int32_t n_bufs,
+                                        void *stream, dd_view_ingest **out) {
+    if (!out || n_rows < 0 || n_bufs < 0 || (n_rows > 0 && !views) ||
+        (n_bufs > 0 && (!data_bufs || !data_buf_lens)))
+        return set_err(DD_ERR_INVALID, "dd_view_ingest_run: null or negative argument");
+    if (((uintptr_t)views & 15) != 0)
+        return set_err(DD_ERR_INVALID, "dd_view_ingest_run: views must be 16-byte aligned");
+    for (int32_t b = 0; b < n_bufs; b++)
+        if (data_buf_lens[b] < 0 || (data_buf_lens[b] > 0 && !data_bufs[b]))
+            return set_err(DD_ERR_INVALID, "dd_view_ingest_run: bad data buffer " +
+                                               std::to_string(b));
+    if (n_rows >= (1ll << 32))
+        return set_err(DD_ERR_UNSUPPORTED, "n_rows >= 2^32: chunk the batch");
+    if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
+    hipStream_t s = (hipStream_t)stream;
+
+    std::unique_ptr<dd_view_ingest> g(new dd_view_ingest());
+    g->n_rows = n_rows;
+    g->n_tiles = (n_rows + DD_VW_TILE_ROWS - 1) / DD_VW_TILE_ROWS;
+    const int64_t nt = g->n_tiles;
+    const int lds = dd_view_lds_enabled();
+    HIP_TRY(hipMalloc((void **)&g->offs, ((size_t)nt * DD_VW_TILE_ROWS + 4) * 4));
+    HIP_TRY(hipMalloc((void **)&g->tsum, (size_t)(2 * nt + 3) * 8));
+    HIP_TRY(hipMalloc((void **)&g->flag, 4));
+    HIP_TRY(hipMalloc(&g->tab, (size_t)(n_bufs ? n_bufs : 1) * 16));
+    for (auto &e : g->ev) HIP_TRY(hipEventCreate(&e));
+    uint64_t *scan = g->tsum + nt, *meta = g->tsum + 2 * nt + 1;
+    const uint8_t *const *d_bufs = (const uint8_t *const *)g->tab;
+    const int64_t *d_lens = (const int64_t *)((char *)g->tab + (size_t)n_bufs * 8);
+    if (n_bufs) {
+        HIP_TRY(hipMemcpyAsync(g->tab, data_bufs, (size_t)n_bufs * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync((void *)d_lens, data_buf_lens, (size_t)n_bufs * 8,
+                               hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemsetAsync(g->flag, 0, 4, s));
+
+    HIP_TRY(hipEventRecord(g->ev[0], s));
+    HIP_TRY(dd_launch_vw_len(views, validity, n_rows, d_lens, n_bufs, g->offs, g->tsum,
+                             g->flag, s));
+    HIP_TRY(hipEventRecord(g->ev[1], s));
+    HIP_TRY(dd_launch_vw_scan(g->tsum, nt, 1, scan, meta, g->offs + n_rows, s));
+    HIP_TRY(dd_launch_vw_add(g->offs, nt, scan, s));
+    HIP_TRY(hipEventRecord(g->ev[2], s));
+
+    /* the one host sync: flag, byte total, and how many tiles outgrow the LDS image */
+    uint32_t flag_h = 0;
+    uint64_t meta_h[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&flag_h, g->flag, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(meta_h, meta, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (flag_h)
+        return set_err(DD_ERR_INVALID,
+                       "view ingest: a valid row has a negative length or points outside "
+                       "its data buffer (buffer_index / offset / length)");
+    if (meta_h[0] > (uint64_t)INT32_MAX)
+        return set_err(DD_ERR_UNSUPPORTED,
+                       "view ingest: value bytes exceed INT32_MAX: chunk the rows");
+    g->data_len = (int64_t)meta_h[0];
+    /* LDS-staged when the knob asks for it, unless every tile outgrew the image */
+    g->tier = lds && (nt == 0 || (int64_t)meta_h[1] < nt);
+    HIP_TRY(hipMalloc((void **)&g->bytes, (size_t)g->data_len + 8));
+    HIP_TRY(hipEventRecord(g->ev[3], s));
+    if (g->data_len)
+        HIP_TRY(dd_launch_vw_copy(views, n_rows, d_bufs, g->offs, g->bytes, g->tier, s));
+    HIP_TRY(hipEventRecord(g->ev[4], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = g.release();
+    return DD_OK;
+}
+
+extern "C" const int32_t *dd_view_ingest_offsets(const dd_view_ingest *g) {
+    return g ? g->offs : nullptr;
+}
+extern "C" const uint8_t *dd_view_ingest_bytes(const dd_view_ingest *g) {
+    return g ? g->bytes : nullptr;
+}
+extern "C" int64_t dd_view_ingest_data_len(const dd_view_ingest *g) {
+    return g ? g->data_len : -1;
+}
+extern "C" int32_t dd_view_ingest_tier(const dd_view_ingest *g) { return g ? g->tier : -1; }
+extern "C" void dd_view_ingest_destroy(dd_view_ingest *g) { delete g; }
+
+extern "C" dd_status dd_view_ingest_kernel_ms(const dd_view_ingest *g, float out_ms[3]) {
+    if (!g || !out_ms) return set_err(DD_ERR_INVALID, "null argument");
+    HIP_TRY(hipEventSynchronize(g->ev[4]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[0], g->ev[0], g->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[1], g->ev[1], g->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[2], g->ev[3], g->ev[4]));
+    return DD_OK;
+}
+
+struct dd_view_emit {
+    const dd_partitioner *p = nullptr;
+    uint32_t W = 0;
+    int64_t n_rows = 0;
+    std::vector<int64_t> long_off; /* host prefix sums [W+1] */
+    dd_vw_tile *tiles = nullptr;
+    uint64_t *tsum = nullptr; /* [n_tiles][2] then the scan [n_tiles+1][2] then meta[3] */
+    void *views = nullptr;
+    uint8_t *bytes = nullptr;
+    hipEvent_t ev[5] = {}; /* scan: 0-1, build: 2-3, copy: 3-4 */
+    ~dd_view_emit() {
+        (void)hipFree(tiles);
+        (void)hipFree(tsum);
+        (void)hipFree(views);
+        (void)hipFree(bytes);
+        for (auto &e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+extern "C" dd_status dd_view_emit_run(const dd_partitioner *p, int32_t col,
+                                      uint32_t n_windows, void *stream, dd_view_emit **out) {
+    if (!p || !out) return set_err(DD_ERR_INVALID, "null argument");
+    if (!p->has_run) return set_err(DD_ERR_INVALID, "partitioner has not run");
+    if (col < 0 || col >= p->batch.n_cols || p->batch.cols[col].dtype != DD_DT_UTF8)
+        return set_err(DD_ERR_INVALID, "view emit needs a utf8 column");
+    if (n_windows == 0 || p->nparts % n_windows != 0)
+        return set_err(DD_ERR_INVALID, "n_windows must be > 0 and divide P_total");
+    int var = -1;
+    for (int v = 0; v < p->ka.n_var; v++)
+        if (p->ka.var_idx[v] == col) var = v;
+    if (var < 0 || !p->out_lengths[col])
+        return set_err(DD_ERR_INVALID, "view emit: column has no var-width output");
+    hipStream_t s = (hipStream_t)stream;
+
+    std::unique_ptr<dd_view_emit> g(new dd_view_emit());
+    g->p = p;
+    g->W = n_windows;
+    g->n_rows = p->batch.n_rows;
+    const uint32_t W = n_windows, ppw = p->nparts / W;
+
+    /* tile table from the host-known row offsets: no tile straddles a partition (hence a
+     * window); empty partitions and windows produce none */
+    std::vector<int64_t> roff(p->nparts + 1);
+    dd_status st = dd_partitioner_row_offsets(p, roff.data());
+    if (st != DD_OK) return st;
+    std::vector<dd_vw_tile> tiles;
+    std::vector<int64_t> win_first(W + 1, 0);
+    for (uint32_t w = 0; w < W; w++) {
+        win_first[w] = (int64_t)tiles.size();
+        for (uint32_t q = w * ppw; q < (w + 1) * ppw; q++) {
+            const uint32_t pf = (uint32_t)tiles.size();
+            for (int64_t r = roff[q]; r < roff[q + 1]; r += DD_VW_TILE_ROWS)
+                tiles.push_back({r, r + DD_VW_TILE_ROWS < roff[q + 1] ? r + DD_VW_TILE_ROWS
+                                                                      : roff[q + 1],
+                                 q, pf, (uint32_t)win_first[w], 0u});
+        }
+    }
+    const int64_t nt = (int64_t)tiles.size();
+    win_first[W] = nt;
+    if (nt > INT32_MAX) return set_err(DD_ERR_UNSUPPORTED, "too many view tiles");
+
+    HIP_TRY(hipMalloc((void **)&g->tiles, (size_t)(nt ? nt : 1) * sizeof(dd_vw_tile)));
+    HIP_TRY(hipMalloc((void **)&g->tsum, (size_t)(4 * nt + 2 + 3) * 8));
+    HIP_TRY(hipMalloc(&g->views, (size_t)g->n_rows * 16 + 16));
+    for (auto &e : g->ev) HIP_TRY(hipEventCreate(&e));
+    uint64_t *S = g->tsum + 2 * nt, *meta = g->tsum + 4 * nt + 2;
+    if (nt)
+        HIP_TRY(hipMemcpyAsync(g->tiles, tiles.data(), (size_t)nt * sizeof(dd_vw_tile),
+                               hipMemcpyHostToDevice, s));
+    const uint32_t *lens = p->out_lengths[col];
+    const uint8_t *valid = p->out_valid[col];
+    const uint8_t *src = (const uint8_t *)p->out_data[col];
+    const uint64_t *pboff = p->part_boffsets + (size_t)var * (p->nparts + 1);
+
+    HIP_TRY(hipEventRecord(g->ev[0], s));
+    HIP_TRY(dd_launch_ve_sums(g->tiles, nt, lens, valid, g->tsum, s));
+    HIP_TRY(dd_launch_vw_scan(g->tsum, nt, 2, S, meta, nullptr, s));
+    HIP_TRY(hipEventRecord(g->ev[1], s));
+
+    /* the one host sync: the long-byte scan, to size the buffer and cut it by window */
+    std::vector<uint64_t> S_h((size_t)2 * (nt + 1));
+    HIP_TRY(hipMemcpyAsync(S_h.data(), S, S_h.size() * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    g->long_off.assign(W + 1, 0);
+    for (uint32_t w = 0; w <= W; w++) g->long_off[w] = (int64_t)S_h[2 * win_first[w] + 1];
+    for (uint32_t w = 0; w < W; w++)
+        if (g->long_off[w + 1] - g->long_off[w] > (int64_t)INT32_MAX)
+            return set_err(DD_ERR_UNSUPPORTED, "view emit: window " + std::to_string(w) +
+                                                   " holds more than INT32_MAX long bytes: "
+                                                   "use more windows");
+    HIP_TRY(hipMalloc((void **)&g->bytes, (size_t)g->long_off[W] + 8));
+    HIP_TRY(hipEventRecord(g->ev[2], s));
+    HIP_TRY(dd_launch_ve_build(g->tiles, nt, lens, valid, src, pboff, S, g->views, s));
+    HIP_TRY(hipEventRecord(g->ev[3], s));
+    if (g->long_off[W])
+        HIP_TRY(dd_launch_ve_copy(g->tiles, nt, lens, valid, src, pboff, S, g->bytes,
+                                  dd_view_lds_enabled(), s));
+    HIP_TRY(hipEventRecord(g->ev[4], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = g.release();
+    return DD_OK;
+}
+
+extern "C" const void *dd_view_emit_views(const dd_view_emit *g) {
+    return g ? g->views : nullptr;
+}
+extern "C" const uint8_t *dd_view_emit_bytes(const dd_view_emit *g) {
+    return g ? g->bytes : nullptr;
+}
+extern "C" void dd_view_emit_destroy(dd_view_emit *g) { delete g; }
+
+extern "C" dd_status dd_view_emit_counts(const dd_view_emit *g, int64_t *long_byte_off) {
+    if (!g || !long_byte_off) return set_err(DD_ERR_INVALID, "null argument");
+    memcpy(long_byte_off, g->long_off.data(), g->long_off.size() * 8);
+    return DD_OK;
+}
+
+extern "C" dd_status dd_view_emit_kernel_ms(const dd_view_emit *g, float out_ms[3]) {
+    if (!g || !out_ms) return set_err(DD_ERR_INVALID, "null argument");
+    HIP_TRY(hipEventSynchronize(g->ev[4]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[0], g->ev[0], g->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[1], g->ev[2], g->ev[3]));
+    HIP_TRY(hipEventElapsedTime(&out_ms[2], g->ev[3], g->ev[4]));
+    return DD_OK;
+}
+
 /* rebase with host tables: uploads them, runs k_gc_rebase, syncs, frees (every path) */
 static dd_status dd_rebase_run(const int32_t *in, int64_t n, const int64_t *host_seg_off,
                                const int32_t *host_bases, int32_t n_seg, int32_t skew,

@@ -99,6 +99,20 @@ struct dd_gc_tile {
 #define DD_GC_GLB_THREADS 256
 #define DD_GC_LDS_MAX_WORDS 16384u /* 64 KiB bitmap = dict_n <= 524288 */
 
+/* view columns (dd_views.hip): a block of DD_VW_THREADS owns a tile of
+ * DD_VW_TILE_ROWS rows and stages up to DD_VW_IMAGE_BYTES of its output in LDS */
+#define DD_VW_THREADS 512
+#define DD_VW_TILE_ROWS 512
+#define DD_VW_IMAGE_BYTES 40960
+/* emit tile: never straddles a partition (hence never a window) */
+struct dd_vw_tile {
+    int64_t row_lo, row_hi; /* partition-major output rows [row_lo, row_hi) */
+    uint32_t part;          /* partition of the rows */
+    uint32_t part_first;    /* first tile of that partition */
+    uint32_t win_first;     /* first tile of the rows' window */
+    uint32_t pad;
+};
+
 #include "dd_shuffle.h" /* dd_status for dd_set_error */
 
 /* DD_PRE_XCD=1 block map of k_scatter_pre. Workgroups are dealt round-robin over
@@ -132,6 +146,25 @@ hipError_t dd_launch_gc_remap(const dd_gc_tile *tiles, int64_t n_tiles, const in
 hipError_t dd_launch_gc_rebase(const int32_t *in, int64_t n, const int64_t *seg_off,
                                const int32_t *bases, int32_t n_seg, int32_t skew,
                                int32_t *out, hipStream_t s);
+hipError_t dd_launch_vw_len(const void *views, const uint8_t *valid, int64_t n_rows,
+                            const int64_t *buf_lens, int32_t n_bufs, int32_t *lens,
+                            uint64_t *tsum, uint32_t *flag, hipStream_t s);
+hipError_t dd_launch_vw_scan(const uint64_t *in, int64_t n, int32_t nc, uint64_t *out,
+                             uint64_t *meta, int32_t *off_end, hipStream_t s);
+hipError_t dd_launch_vw_add(int32_t *offs, int64_t n_tiles, const uint64_t *tbase,
+                            hipStream_t s);
+hipError_t dd_launch_vw_copy(const void *views, int64_t n_rows, const uint8_t *const *bufs,
+                             const int32_t *offs, uint8_t *out, int lds, hipStream_t s);
+hipError_t dd_launch_ve_sums(const dd_vw_tile *tiles, int64_t n_tiles, const uint32_t *lens,
+                             const uint8_t *valid, uint64_t *tsum, hipStream_t s);
+hipError_t dd_launch_ve_build(const dd_vw_tile *tiles, int64_t n_tiles, const uint32_t *lens,
+                              const uint8_t *valid, const uint8_t *bytes,
+                              const uint64_t *part_boff, const uint64_t *S, void *views,
+                              hipStream_t s);
+hipError_t dd_launch_ve_copy(const dd_vw_tile *tiles, int64_t n_tiles, const uint32_t *lens,
+                             const uint8_t *valid, const uint8_t *bytes,
+                             const uint64_t *part_boff, const uint64_t *S, uint8_t *out,
+                             int lds, hipStream_t s);
 dd_status dd_set_error(dd_status s, const char *msg); /* thread-local dd_last_error */
 hipError_t dd_launch_dict_hashes(const uint8_t *bytes, const int32_t *offsets, int64_t n,
                                  uint64_t *out, hipStream_t s);

@@ -297,6 +297,72 @@ dd_status dd_dict_rebase(const int32_t *in, int64_t n, const int64_t *host_seg_o
                          const int32_t *host_bases, int32_t n_seg, int32_t *out,
                          void *stream);
 
+/* ---------------- view columns (Utf8View / BinaryView around the shuffle) ----------------
+ * Besides dictionaries, the reference's pre-wire GC calls .gc() on StringViewArray and
+ * BinaryViewArray so that their buffers hold only referenced bytes (garbage_collect_arrays,
+ * src/protocol/grpc/worker_service.rs:408-433). The device's var-width form (dense offsets +
+ * bytes) is that form already, so view columns get two steps around the unchanged
+ * partitioner and exchange (normative): INGEST turns views + N data buffers
+ * into an ordinary DD_DT_UTF8 column, EMIT turns a partition-major utf8 column into compact
+ * per-window view arrays. Arrow view layout, little-endian, 16 bytes per row: i32 length;
+ * length <= 12: the value, zero-padded; else a 4-byte prefix, i32 buffer_index, i32 offset. */
+
+typedef struct dd_view_ingest dd_view_ingest; /* opaque, owns offsets + bytes */
+
+/* worker_service.rs:408-433 (gc() of a view array, device side). views: device, 16-byte
+ * aligned, 16 B x n_rows; validity: device unpacked u8 or NULL; data_bufs / data_buf_lens:
+ * HOST arrays of n_bufs device pointers / byte lengths. Row i has len = view.length if
+ * valid, else 0 (a null row's view is never interpreted); offsets = exclusive prefix sum of
+ * len; bytes = the values in row order. Views may alias, overlap, repeat, and come in any
+ * order. n_bufs == 0 (every valid row inline) and n_rows == 0 are legal. A valid row with
+ * length < 0, or a long row with buffer_index outside [0, n_bufs), offset < 0 or offset +
+ * length > data_buf_lens[buffer_index], is never dereferenced: DD_ERR_INVALID. Value bytes
+ * above INT32_MAX: DD_ERR_UNSUPPORTED before any copy (chunk the rows). Synchronous: one
+ * host sync reads the flag and the total and sizes the bytes. The result is an ordinary
+ * DD_DT_UTF8 column: data = bytes, offsets, data_len. */
+dd_status dd_view_ingest_run(const void *views, const uint8_t *validity, int64_t n_rows,
+                             const void *const *data_bufs, const int64_t *data_buf_lens,
+                             int32_t n_bufs, void *stream, dd_view_ingest **out);
+/* worker_service.rs:408-433: device i32[n_rows+1], zero-based */
+const int32_t *dd_view_ingest_offsets(const dd_view_ingest *g);
+/* worker_service.rs:408-433: device value bytes, data_len of them */
+const uint8_t *dd_view_ingest_bytes(const dd_view_ingest *g);
+int64_t dd_view_ingest_data_len(const dd_view_ingest *g);
+/* copy tier of the run: 1 = LDS-staged (DD_VIEW_LDS=1, read per call; a tile whose bytes
+ * outgrow the image still copies directly), 0 = direct (the default: DD_VIEW_LDS unset or
+ * 0, or every tile outgrew the image) */
+int32_t dd_view_ingest_tier(const dd_view_ingest *g);
+/* hipEvent durations of the run in ms: length pass, scan, copy */
+dd_status dd_view_ingest_kernel_ms(const dd_view_ingest *g, float out_ms[3]);
+void dd_view_ingest_destroy(dd_view_ingest *g);
+/* rows per copy tile and bytes of the LDS image (tests size their edge cases from these) */
+int32_t dd_view_tile_rows(void);
+int32_t dd_view_image_bytes(void);
+
+typedef struct dd_view_emit dd_view_emit; /* opaque: views + per-window data buffers */
+
+/* worker_service.rs:408-433 (the arrays gc() would produce, per window). `col` is a UTF8
+ * column of a run partitioner; windows as for the dictionary GC (n_windows divides P_total,
+ * each window a contiguous partition range), anything else DD_ERR_INVALID. Window w's data
+ * buffer is the concatenation, in row order, of its valid rows' values longer than 12
+ * bytes. A null row emits 16 zero bytes; a valid short row its length and value; a valid
+ * long row its length, 4-byte prefix, buffer_index 0 and offset = the long bytes of earlier
+ * rows of the window. Any row slice of a window plus the window's buffer is a valid Arrow
+ * view array. A window with more than INT32_MAX long bytes: DD_ERR_UNSUPPORTED.
+ * Synchronous; `stream` must be ordered after the partitioner's run. The partitioner's own
+ * output is not modified and must outlive the emit object. */
+dd_status dd_view_emit_run(const dd_partitioner *p, int32_t col, uint32_t n_windows,
+                           void *stream, dd_view_emit **out);
+/* worker_service.rs:408-433: device 16 B x n_rows, partition-major */
+const void *dd_view_emit_views(const dd_view_emit *g);
+/* host prefix sums [n_windows+1] of the windows' data buffer sizes */
+dd_status dd_view_emit_counts(const dd_view_emit *g, int64_t *long_byte_off);
+/* device: window w's data buffer starts at long_byte_off[w] */
+const uint8_t *dd_view_emit_bytes(const dd_view_emit *g);
+/* hipEvent durations of the run in ms: scan, build, copy */
+dd_status dd_view_emit_kernel_ms(const dd_view_emit *g, float out_ms[3]);
+void dd_view_emit_destroy(dd_view_emit *g);
+
 /* ---------------- coalesce (N->M task coalesce, no repartition) ----------------
  * Data plane for NetworkCoalesceExec (src/execution_plans/network_coalesce.rs:24-70):
  * consumer rank t receives the WHOLE partitioned output of every producer rank in its
