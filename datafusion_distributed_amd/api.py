@@ -21,11 +21,13 @@ STATUS_NAMES = {
 }
 
 DTYPE_CODE = {"u8": 1, "i16": 2, "i32": 3, "i64": 4, "f32": 5, "f64": 6,
-              "bool": 7, "utf8": 8, "dict32": 9}
+              "bool": 7, "utf8": 8, "dict32": 9, "dec128": 10}
+# dec128: one value is two u64 words [lo, hi]; host arrays are (n, 2)
 FIXED_NP = {"u8": np.uint8, "bool": np.uint8, "i16": np.int16, "i32": np.int32,
-            "f32": np.float32, "i64": np.int64, "f64": np.float64, "dict32": np.int32}
+            "f32": np.float32, "i64": np.int64, "f64": np.float64, "dict32": np.int32,
+            "dec128": np.uint64}
 ELEM_SIZE = {"u8": 1, "bool": 1, "i16": 2, "i32": 4, "f32": 4, "i64": 8, "f64": 8,
-             "dict32": 4}
+             "dict32": 4, "dec128": 16}
 
 DD_MAX_COLS = 24
 UNIQUE_ID_BYTES = 128
@@ -176,6 +178,47 @@ def _d2h(src_ptr, nbytes, dtype):
     return out
 
 
+def fixed_host(col):
+    """The host array of a fixed-width column dict in its canonical dtype and shape. A
+    dec128 column may hold any C-contiguous array of n x 16 bytes; it comes back as u64
+    (n, 2) = [lo, hi] without a copy."""
+    if col["dtype"] == "dec128":
+        data = np.asarray(col["data"])
+        if data.dtype != np.uint64 or data.ndim != 2 or not data.flags.c_contiguous:
+            if not data.flags.c_contiguous or data.nbytes % 16:
+                raise ValueError("dec128 data must be a C-contiguous array of n x 16 bytes")
+            data = data.reshape(-1).view(np.uint8).view(np.uint64)
+        return data.reshape(-1, 2)
+    return np.ascontiguousarray(col["data"], dtype=FIXED_NP[col["dtype"]])
+
+
+def fixed_out(dtype, flat):
+    """Shape a downloaded fixed-width buffer like fixed_host: dec128 -> u64 (n, 2)."""
+    return flat.reshape(-1, 2) if dtype == "dec128" else flat
+
+
+def dec128_col(arr):
+    """Column dict of a pyarrow Decimal128Array: the value buffer as u64 (n, 2) = [lo, hi],
+    the validity bitmap unpacked to u8 (None when the array has no nulls), and precision and
+    scale from the type, which only the Arrow boundary reads back."""
+    import pyarrow as pa
+
+    if isinstance(arr, pa.ChunkedArray):
+        arr = arr.combine_chunks()
+    if not pa.types.is_decimal128(arr.type):
+        raise TypeError(f"dec128_col needs a decimal128 array, got {arr.type}")
+    n = len(arr)
+    bitmap, values = arr.buffers()
+    data = np.zeros((0, 2), dtype=np.uint64) if n == 0 else np.frombuffer(
+        values, dtype=np.uint64, count=2 * n, offset=16 * arr.offset).reshape(n, 2).copy()
+    valid = None
+    if arr.null_count:
+        bits = np.unpackbits(np.frombuffer(bitmap, dtype=np.uint8), bitorder="little")
+        valid = np.ascontiguousarray(bits[arr.offset:arr.offset + n])
+    return {"dtype": "dec128", "data": data, "valid": valid,
+            "precision": arr.type.precision, "scale": arr.type.scale}
+
+
 class DeviceBatch:
     """Device-resident batch uploaded from the column-dict convention."""
 
@@ -185,6 +228,8 @@ class DeviceBatch:
             self.n_rows = len(cols[0]["offsets"]) - 1
         elif cols[0]["dtype"] == "utf8view":
             self.n_rows = len(np.asarray(cols[0]["views"], dtype=np.uint8).reshape(-1, 16))
+        elif cols[0]["dtype"] == "dec128":
+            self.n_rows = len(fixed_host(cols[0]))
         else:
             self.n_rows = len(cols[0]["data"])
         self._bufs = []
@@ -209,8 +254,10 @@ class DeviceBatch:
                 cd.data_len = int(data.nbytes)
                 self._utf8_maxlen[i] = int(np.diff(off).max()) if len(off) > 1 else 0
             else:
-                npdt = FIXED_NP[col["dtype"]]
-                data = np.ascontiguousarray(col["data"], dtype=npdt)
+                data = fixed_host(col)
+                if col["dtype"] == "dec128" and len(data) != self.n_rows:
+                    raise ValueError(f"column {i} has {len(data)} rows, batch has "
+                                     f"{self.n_rows}")
                 cd.data = self._up(data)
                 cd.data_len = 0
             if col.get("valid") is not None:
@@ -323,7 +370,7 @@ class DeviceBatch:
                                      f"{longest} bytes")
                 plan += [(cd.data, data), (cd.offsets, off)]
             else:
-                data = np.ascontiguousarray(col["data"], dtype=FIXED_NP[col["dtype"]])
+                data = fixed_host(col)
                 if len(data) != n:
                     raise ValueError(f"refill: column {i} has {len(data)} rows, "
                                      f"batch has {n}")
@@ -500,8 +547,9 @@ class Partitioner:
                                   np.uint32)
         else:
             npdt = FIXED_NP[col["dtype"]]
-            res["data"] = _d2h(lib().dd_partitioner_col_data(self.h, i),
-                               n * ELEM_SIZE[col["dtype"]], npdt)
+            res["data"] = fixed_out(col["dtype"],
+                                    _d2h(lib().dd_partitioner_col_data(self.h, i),
+                                         n * ELEM_SIZE[col["dtype"]], npdt))
         vp = lib().dd_partitioner_col_validity(self.h, i)
         if vp:
             res["valid"] = _d2h(vp, n, np.uint8)
@@ -778,8 +826,8 @@ class Broadcasted:
             out["offsets"] = _d2h(lib().dd_bcast_col_offsets(self.h, i), (n + 1) * 4,
                                   np.int32)
         else:
-            out["data"] = _d2h(lib().dd_bcast_col_data(self.h, i), int(dlen.value),
-                               FIXED_NP[name])
+            out["data"] = fixed_out(name, _d2h(lib().dd_bcast_col_data(self.h, i),
+                                               int(dlen.value), FIXED_NP[name]))
         vp = lib().dd_bcast_col_validity(self.h, i)
         if vp:
             out["valid"] = _d2h(vp, n, np.uint8)
@@ -829,8 +877,9 @@ class Exchanged:
             return {"dtype": "utf8", "data": data, "lengths": lens}
         npdt = FIXED_NP[col["dtype"]]
         return {"dtype": col["dtype"],
-                "data": _d2h(lib().dd_exchanged_col_data(self.h, i),
-                             n * ELEM_SIZE[col["dtype"]], npdt)}
+                "data": fixed_out(col["dtype"],
+                                  _d2h(lib().dd_exchanged_col_data(self.h, i),
+                                       n * ELEM_SIZE[col["dtype"]], npdt))}
 
     def col_validity(self, i):
         vp = lib().dd_exchanged_col_validity(self.h, i)

@@ -130,6 +130,14 @@ def partition_batches(part, lo, hi, batch_size=8192, gc=None, views=None):
                     idx = pa.array(fixed[i][b0:b1], type=pa.int32(), mask=mask)
                     values = _utf8_values(pa, c["dict_offsets"], c["dict_bytes"])
                     arr = pa.DictionaryArray.from_arrays(idx, values)
+                elif c["dtype"] == "dec128":
+                    # the partition-major buffer is already Arrow's value buffer; precision
+                    # and scale come from the schema (the column dict), DESIGN.md §16
+                    arr = pa.Array.from_buffers(
+                        pa.decimal128(c.get("precision", 38), c.get("scale", 0)), b1 - b0,
+                        [pa.py_buffer(np.packbits(~mask, bitorder="little").tobytes())
+                         if mask is not None else None,
+                         pa.py_buffer(fixed[i][b0:b1].tobytes())])
                 elif c["dtype"] == "bool":
                     arr = pa.array(fixed[i][b0:b1].astype(bool), type=pa.bool_(), mask=mask)
                 else:

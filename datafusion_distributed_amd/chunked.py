@@ -30,7 +30,9 @@ def chunked_partition(cols, key_idx, nparts, max_chunk_rows=2**31,
     """Returns {"part_row_offsets", "cols": [{"dtype", "data"(np), "valid", "lengths"}...]}
     — downloaded final buffers (harness/test use; a production caller would keep the
     device pointers)."""
-    n = (len(cols[0]["offsets"]) - 1 if cols[0]["dtype"] == "utf8" else len(cols[0]["data"]))
+    n = (len(cols[0]["offsets"]) - 1 if cols[0]["dtype"] == "utf8"
+         else len(api.fixed_host(cols[0])) if cols[0]["dtype"] == "dec128"
+         else len(cols[0]["data"]))
 
     # choose chunk boundaries respecting both caps
     bounds = [0]
@@ -62,6 +64,8 @@ def chunked_partition(cols, key_idx, nparts, max_chunk_rows=2**31,
                 off = c["offsets"]
                 sc["offsets"] = (off[lo:hi + 1] - off[lo]).astype(np.int32)
                 sc["data"] = c["data"][int(off[lo]):int(off[hi])]
+            elif c["dtype"] == "dec128":
+                sc["data"] = api.fixed_host(c)[lo:hi]  # rows of [lo, hi] words
             else:
                 sc["data"] = c["data"][lo:hi]
             if c.get("valid") is not None:
@@ -152,7 +156,8 @@ def chunked_partition(cols, key_idx, nparts, max_chunk_rows=2**31,
             oc["lengths"] = api._d2h(final[i]["lengths"].value, total_rows * 4, np.uint32)
         else:
             npdt = api.FIXED_NP[c["dtype"]]
-            oc["data"] = api._d2h(final[i]["data"].value, total_rows * elem[i], npdt)
+            oc["data"] = api.fixed_out(
+                c["dtype"], api._d2h(final[i]["data"].value, total_rows * elem[i], npdt))
         if c.get("valid") is not None:
             oc["valid"] = api._d2h(final[i]["valid"].value, total_rows, np.uint8)
         out_cols.append(oc)

@@ -82,14 +82,34 @@ __device__ __forceinline__ uint64_t dd_value_hash_dev(const dd_kcol &c, int64_t 
 }
 
 
-/* row hash over the key columns; create_hashes restatement */
+/* one 16-byte value (dec128 and its layout kin): x = lo = bytes 0..7, y = hi = bytes
+ * 8..15. A native vector, so a load or store of it is one 128-bit access */
+typedef uint64_t dd_u128 __attribute__((ext_vector_type(2)));
+
+/* §3.1's comb */
+__device__ __forceinline__ uint64_t dd_hash_comb(uint64_t h, uint64_t vh) {
+    return h ^ (vh + 0x9e3779b97f4a7c15ULL + (h << 6) + (h >> 2));
+}
+
+/* row hash over the key columns; create_hashes restatement.
+ * DEC128 = false: for callers whose host gate admits no dec128 key (the pre-path K1 kernels,
+ * the partial reduce); they compile to what they were before the dtype existed. */
+template <bool DEC128 = true>
 __device__ __forceinline__ uint64_t dd_row_hash(const dd_kargs &a, int64_t i) {
     uint64_t h = 0;
     for (int k = 0; k < a.n_keys; k++) {
         const dd_kcol &c = a.cols[a.key_idx[k]];
         if (c.valid && !c.valid[i]) continue;
+        if (DEC128 && c.dtype == DD_KDT_DEC128) {
+            /* §16: hashes as the two i64 keys (lo, hi) in that order; one 16-byte load
+             * (the host checks the alignment) */
+            const dd_u128 v = ((const dd_u128 *)c.data)[i];
+            h = dd_hash_comb(h, dd_mix64(v.x));
+            h = dd_hash_comb(h, dd_mix64(v.y));
+            continue;
+        }
         uint64_t vh = dd_value_hash_dev(c, i);
-        h = h ^ (vh + 0x9e3779b97f4a7c15ULL + (h << 6) + (h >> 2));
+        h = dd_hash_comb(h, vh);
     }
     return h;
 }

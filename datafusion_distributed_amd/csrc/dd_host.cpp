@@ -121,6 +121,8 @@ static int fixed_elem_size(int dtype) {
     case DD_DT_I64:
     case DD_DT_F64:
         return 8;
+    case DD_DT_DEC128:
+        return 16;
     default:
         return 0; /* utf8 */
     }
@@ -279,6 +281,9 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
         kc.data = cd.data;
         kc.valid = cd.validity;
         kc.offsets = cd.offsets;
+        /* the kernels move a dec128 value with one 16-byte access */
+        if (cd.dtype == DD_DT_DEC128 && ((uintptr_t)cd.data & 15) != 0)
+            return fail(DD_ERR_INVALID, "dec128 column data must be 16-byte aligned");
         if (cd.dtype == DD_DT_UTF8) {
             if (ka.n_var >= DD_KMAX_VAR) return fail(DD_ERR_UNSUPPORTED, "too many var columns");
             /* Arrow utf8 offsets are int32: a column past INT32_MAX bytes has already
@@ -305,8 +310,10 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
     if (aug_cols <= DD_STAGE_MAXC && (nvar == 0 || allow_staged_var)) {
         size_t row_stage = 4; /* dstg */
         int nvalid = 0;
+        bool has16 = false; /* a dec128 column: 16-byte image slots, W16 kernel form */
         for (int c = 0; c < batch->n_cols; c++) {
             row_stage += fixed_elem_size(batch->cols[c].dtype);
+            if (fixed_elem_size(batch->cols[c].dtype) == 16) has16 = true;
             if (batch->cols[c].validity) nvalid++;
         }
         row_stage += nvalid;
@@ -331,6 +338,9 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
             /* k_scatter_staged is instantiated for (gmax, wpb) in {2,4,8}x{4,8} and
              * {2,4}x{16} */
             int gcap = (wpb == 16) ? 4 : 8;
+            /* W16 forms past 4 columns exist up to gmax 2 / 4 / 8 at wpb 16 / 8 / 4 (their
+             * second value register per row group; DD_CASE16 in dd_launch_scatter_staged) */
+            if (has16 && aug_cols > 4) gcap = (wpb == 16) ? 2 : (wpb == 8) ? 4 : 8;
             int gtop = 2;
             while (gtop < gcap && (size_t)gtop * wpb * 64 < 32 * (size_t)P) gtop *= 2;
             if (const char *e = getenv("DD_V2_GMAX")) {
@@ -557,7 +567,8 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
         p->wpb == 16 && nvar == 0 && batch->n_cols <= DD_STAGE_MAXC) {
         bool rhash = true;
         for (int c = 0; c < batch->n_cols && rhash; c++)
-            if (batch->cols[c].validity || fixed_elem_size(batch->cols[c].dtype) == 0)
+            if (batch->cols[c].validity || fixed_elem_size(batch->cols[c].dtype) == 0 ||
+                fixed_elem_size(batch->cols[c].dtype) > 8) /* no 16-byte spec form */
                 rhash = false;
         for (int k = 0; k < n_keys && rhash; k++) {
             const int dt = batch->cols[key_cols[k]].dtype;
@@ -2206,12 +2217,17 @@ extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
         if (batch->cols[key_cols[k]].dtype == DD_DT_UTF8)
             return set_err(DD_ERR_UNSUPPORTED,
                            "partial reduce: fixed-width or dictionary keys only");
+        if (batch->cols[key_cols[k]].dtype == DD_DT_DEC128)
+            return set_err(DD_ERR_UNSUPPORTED, "partial reduce: dec128 keys are not supported");
     }
     for (int g = 0; g < n_aggs; g++) {
         if (agg_ops[g] == DD_AGG_COUNT) continue;
         if (!agg_cols || agg_cols[g] < 0 || agg_cols[g] >= batch->n_cols)
             return set_err(DD_ERR_INVALID, "agg column out of range");
         int dt = batch->cols[agg_cols[g]].dtype;
+        if (dt == DD_DT_DEC128)
+            return set_err(DD_ERR_UNSUPPORTED,
+                           "partial reduce: dec128 aggregate inputs are not supported");
         if ((agg_ops[g] == DD_AGG_SUM_F64 || agg_ops[g] == DD_AGG_MIN_F64 ||
              agg_ops[g] == DD_AGG_MAX_F64) &&
             dt != DD_DT_F64)

@@ -33,6 +33,7 @@ enum {
     DD_KDT_BOOL = 7,
     DD_KDT_UTF8 = 8,
     DD_KDT_DICT32 = 9,
+    DD_KDT_DEC128 = 10, /* 16-byte value: hashes as two u64 halves (lo, hi), DESIGN.md §16 */
     DD_KDT_VARLEN = 100, /* synthetic (staged-var): data = var col's offsets; value = len */
     DD_KDT_ROWID = 101,  /* synthetic (staged-var): value = input row index */
 };
@@ -54,7 +55,7 @@ enum {
 
 struct dd_kcol {
     int32_t dtype;
-    int32_t elem;               /* fixed elem size (1/2/4/8); 0 for var (utf8) data */
+    int32_t elem;               /* fixed elem size (1/2/4/8/16); 0 for var (utf8) data */
     const void *data;           /* input values / utf8 bytes */
     const uint8_t *valid;       /* unpacked u8, or null */
     const int32_t *offsets;     /* utf8 input offsets[n+1] */

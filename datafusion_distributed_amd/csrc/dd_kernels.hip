@@ -329,6 +329,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_scatter(
                 case 8:
                     ((uint64_t *)col.out_data)[dst] = ((const uint64_t *)col.data)[row];
                     break;
+                case 16: /* one 16-byte load and store per lane */
+                    ((dd_u128 *)col.out_data)[dst] = ((const dd_u128 *)col.data)[row];
+                    break;
                 default:
                     break; /* var col: handled below */
                 }
@@ -496,8 +499,17 @@ __device__ __forceinline__ void dd_block_excl_scan(const uint32_t *vals, uint32_
  * slower at the bench shape, tools/ablate_k3.cpp). NC == 0: generic.
  * RHASH: recompute the row hash from the preloaded register values instead of reading
  * pid_in — the key columns are already in colv, so the pid array's HBM round trip
- * (write in K1 + read here) disappears. Spec paths only (host gate: ka.rhash). */
-template <int GMAX, int WPB, int MAXC, bool HASVAR, int NC = 0, bool RHASH = false>
+ * (write in K1 + read here) disappears. Spec paths only (host gate: ka.rhash).
+ * W16: the batch has a 16-byte column (dec128). Such a column carries its
+ * high half in a second colv slot (one array: two separate ones end up in scratch), takes
+ * 16-byte slots in the LDS image and moves with one 128-bit LDS / global access per row in
+ * place and flush. Every column region of the image starts 16-byte aligned, as a 128-bit
+ * LDS access needs to run at full rate: smem is aligned(16), stage0 sits at
+ * P*(16 + 4*WPB) + 4*BT + 4*R with WPB in {4,8,16}, and regions advance by R*elem and
+ * (validity) R, R a multiple of 256. Generic form only (NC == 0; host and launcher gate
+ * every specialised tier on elem <= 8); with W16 false nothing below changes. */
+template <int GMAX, int WPB, int MAXC, bool HASVAR, int NC = 0, bool RHASH = false,
+          bool W16 = false>
 __global__ __launch_bounds__(WPB * WAVE) void k_scatter_staged(
     dd_kargs a, int64_t tile_rows, uint32_t nparts, int nbits, const uint32_t *pid_in,
     const uint32_t *tile_off /* [nblocks][P] excl within partition */,
@@ -540,8 +552,11 @@ __global__ __launch_bounds__(WPB * WAVE) void k_scatter_staged(
      * loads overlap the previous round's flush */
     uint32_t pidr[GMAX], rankr[GMAX];
     bool actr[GMAX];
-    uint64_t colv[GMAX][MAXC];
+    /* W16: slot MAXC + c holds the high half of a 16-byte value of column c */
+    uint64_t colv[GMAX][W16 ? 2 * MAXC : MAXC];
     uint8_t valv[GMAX][MAXC];
+    static_assert(!W16 || (NC == 0 && !RHASH), "16-byte columns take the generic form");
+    static_assert(R % 256 == 0, "image regions must stay 16-byte aligned");
 
     auto preload = [&](int64_t rstart, int64_t rend) {
         const int64_t segstart = rstart + (int64_t)wid * SEG;
@@ -603,6 +618,13 @@ __global__ __launch_bounds__(WPB * WAVE) void k_scatter_staged(
                     case 2: colv[g][c] = ((const uint16_t *)col.data)[row]; break;
                     case 4: colv[g][c] = ((const uint32_t *)col.data)[row]; break;
                     case 8: colv[g][c] = ((const uint64_t *)col.data)[row]; break;
+                    case 16:
+                        if constexpr (W16) {
+                            const dd_u128 v = ((const dd_u128 *)col.data)[row];
+                            colv[g][c] = v.x;
+                            colv[g][MAXC + c] = v.y;
+                        }
+                        break;
                     }
                 }
                 if (NC == 0 && col.valid) valv[g][c] = col.valid[row];
@@ -712,6 +734,10 @@ __global__ __launch_bounds__(WPB * WAVE) void k_scatter_staged(
                 case 2: ((uint16_t *)stage)[slot] = (uint16_t)colv[g][c]; break;
                 case 4: ((uint32_t *)stage)[slot] = (uint32_t)colv[g][c]; break;
                 case 8: ((uint64_t *)stage)[slot] = colv[g][c]; break;
+                case 16:
+                    if constexpr (W16)
+                        ((dd_u128 *)stage)[slot] = dd_u128{colv[g][c], colv[g][MAXC + c]};
+                    break;
                 }
                 stage += (size_t)R * col.elem;
                 if (NC == 0 && col.valid) {
@@ -749,6 +775,10 @@ __global__ __launch_bounds__(WPB * WAVE) void k_scatter_staged(
                     break;
                 case 8:
                     ((uint64_t *)col.out_data)[dst] = ((const uint64_t *)stage)[i];
+                    break;
+                case 16:
+                    if constexpr (W16)
+                        ((dd_u128 *)col.out_data)[dst] = ((const dd_u128 *)stage)[i];
                     break;
                 }
                 stage += (size_t)R * col.elem;
@@ -2019,7 +2049,7 @@ __global__ __launch_bounds__(BLOCK_THREADS) void k_hash_count_seg(
             actu[u] = row < end;
             pidu[u] = 0;
             if (actu[u]) {
-                uint64_t h = dd_row_hash(a, row);
+                uint64_t h = dd_row_hash<false>(a, row); /* pre path: no dec128 */
                 const uint32_t tot = a.pid_total;
                 uint32_t fine = ((tot & (tot - 1)) == 0)
                                     ? (uint32_t)(h & (uint64_t)(tot - 1))
@@ -2096,7 +2126,7 @@ __global__ __launch_bounds__(16 * WAVE) void k_hash_count_round(
             actu[u] = row < end;
             pidu[u] = 0;
             if (actu[u]) {
-                uint64_t h = dd_row_hash(a, row);
+                uint64_t h = dd_row_hash<false>(a, row); /* pre path: no dec128 */
                 const uint32_t totp = a.pid_total;
                 uint32_t fine = ((totp & (totp - 1)) == 0)
                                     ? (uint32_t)(h & (uint64_t)(totp - 1))
@@ -3104,10 +3134,17 @@ hipError_t dd_launch_scatter_staged(const dd_kargs *a, int64_t nblocks, int64_t 
     }
     const int maxc = (a->n_cols <= 4) ? 4 : 8;
     const bool hasvar = a->n_var > 0;
+    /* a 16-byte column (dec128): the NC > 0 forms below have no case for it and would skip
+     * it silently, so every one of their gates refuses elem > 8; the batch takes the W16
+     * generic form at the end */
+    bool has16 = false;
+    for (int c = 0; c < a->n_cols; c++)
+        if (a->cols[c].elem > 8) has16 = true;
     /* specialized fast path: wpb 16, <=4 fixed columns, no validity, no var */
     bool can_spec = !hasvar && wpb == 16 && a->n_cols <= 4;
     for (int c = 0; c < a->n_cols && can_spec; c++)
-        if (a->cols[c].valid || a->cols[c].elem == 0) can_spec = false;
+        if (a->cols[c].valid || a->cols[c].elem == 0 || a->cols[c].elem > 8)
+            can_spec = false;
 #define DD_SPEC(G, N)                                                                        \
     if (can_spec && gmax == G && a->n_cols == N) {                                           \
         return a->rhash ? dd_launch_spec1<G, 4, N, true>(a, grid, tile_rows, nparts, nbits,  \
@@ -3138,7 +3175,8 @@ hipError_t dd_launch_scatter_staged(const dd_kargs *a, int64_t nblocks, int64_t 
     }
     bool can_spec8 = !hasvar && wpb == 16 && a->n_cols >= 5 && a->n_cols <= 8;
     for (int c = 0; c < a->n_cols && can_spec8; c++)
-        if (a->cols[c].valid || a->cols[c].elem == 0) can_spec8 = false;
+        if (a->cols[c].valid || a->cols[c].elem == 0 || a->cols[c].elem > 8)
+            can_spec8 = false;
     DD_SPEC8(2, 5)
     DD_SPEC8(2, 6)
     DD_SPEC8(2, 7)
@@ -3154,7 +3192,7 @@ hipError_t dd_launch_scatter_staged(const dd_kargs *a, int64_t nblocks, int64_t 
      * loop measured 8-15% slower on the spec path in round 1 — same reasoning here. */
     bool can_specv = hasvar && wpb == 16 && a->n_cols <= 8;
     for (int c = 0; c < a->n_cols && can_specv; c++)
-        if (a->cols[c].valid) can_specv = false;
+        if (a->cols[c].valid || a->cols[c].elem > 8) can_specv = false;
 #define DD_SPECV(G, N)                                                                       \
     if (can_specv && gmax == G && a->n_cols == N) {                                          \
         return dd_launch_spec1<G, 8, N, false, true>(a, grid, tile_rows, nparts, nbits,      \
@@ -3179,6 +3217,43 @@ hipError_t dd_launch_scatter_staged(const dd_kargs *a, int64_t nblocks, int64_t 
     /* rhash batches MUST take a spec path above (no pid array exists to read) — fail
      * loudly rather than fall through to a pid-consuming variant */
     if (a->rhash) return hipErrorInvalidValue;
+    /* generic form with 16-byte slots (W16). colv then holds 4 * gmax * maxc VGPRs, so the
+     * (gmax, wpb, maxc) set stops where that passes half the wave's register budget; the
+     * host caps gmax to match (dd_partitioner_create, has16). A shape outside the table is
+     * an error, never a narrower kernel. */
+#define DD_CASE16(G, W, C, V)                                                                \
+    if (gmax == G && wpb == W && maxc == C && hasvar == V) {                                 \
+        if (lds_bytes > 65536) {                                                             \
+            hipError_t e = hipFuncSetAttribute(                                              \
+                (const void *)k_scatter_staged<G, W, C, V, 0, false, true>,                  \
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);                 \
+            if (e != hipSuccess) return e;                                                   \
+        }                                                                                    \
+        hipLaunchKernelGGL((k_scatter_staged<G, W, C, V, 0, false, true>), grid,             \
+                           dim3(W * WAVE), lds_bytes, s, *a, tile_rows, nparts, nbits,       \
+                           pid_in, tile_off, part_offsets);                                  \
+        return hipGetLastError();                                                            \
+    }
+#define DD_CASE16V(G, W, C) DD_CASE16(G, W, C, false) DD_CASE16(G, W, C, true)
+    if (has16) {
+        DD_CASE16V(2, 4, 4)
+        DD_CASE16V(4, 4, 4)
+        DD_CASE16V(8, 4, 4)
+        DD_CASE16V(2, 4, 8)
+        DD_CASE16V(4, 4, 8)
+        DD_CASE16V(8, 4, 8)
+        DD_CASE16V(2, 8, 4)
+        DD_CASE16V(4, 8, 4)
+        DD_CASE16V(8, 8, 4)
+        DD_CASE16V(2, 8, 8)
+        DD_CASE16V(4, 8, 8)
+        DD_CASE16V(2, 16, 4)
+        DD_CASE16V(4, 16, 4)
+        DD_CASE16V(2, 16, 8)
+        return hipErrorInvalidValue;
+    }
+#undef DD_CASE16V
+#undef DD_CASE16
 #define DD_CASE(G, W, C, V)                                                                  \
     if (gmax == G && wpb == W && maxc == C && hasvar == V) {                                 \
         if (lds_bytes > 65536) {                                                             \

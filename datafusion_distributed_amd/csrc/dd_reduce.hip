@@ -133,7 +133,7 @@ extern "C" __global__ __launch_bounds__(R_THREADS) void k_partial_reduce(
     const int64_t end = (start + chunk_rows < a.n_rows) ? (start + chunk_rows) : a.n_rows;
 
     for (int64_t row = start + threadIdx.x; row < end; row += R_THREADS) {
-        uint64_t h = dd_row_hash(a, row);
+        uint64_t h = dd_row_hash<false>(a, row); /* host refuses dec128 keys */
         if (h == 0) h = 1; /* 0 is the empty sentinel */
         uint64_t kb[4];
         uint32_t knull = 0;

@@ -379,6 +379,12 @@ extern "C" dd_status dd_ipc_writer_create(const dd_ipc_field *fields, int32_t n_
                                 "(arrow_boundary); DictionaryBatch messages are out of "
                                 "tier scope");
         }
+        if (fields[i].dtype == DD_DT_DEC128) {
+            delete w;
+            return dd_set_error(DD_ERR_UNSUPPORTED,
+                                "dec128 columns are not on the wire: dd_ipc_field carries no "
+                                "precision and scale (DESIGN.md §16)");
+        }
         w->cols.push_back({fields[i].dtype,
                            fields[i].name ? fields[i].name : ("f" + std::to_string(i)),
                            fields[i].nullable});

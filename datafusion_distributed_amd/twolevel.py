@@ -27,7 +27,9 @@ def two_level_partition(cols, key_idx, nparts, buckets=8):
     assert nparts & (nparts - 1) == 0
     S = nparts // buckets
     L = api.lib()
-    n = (len(cols[0]["offsets"]) - 1 if cols[0]["dtype"] == "utf8" else len(cols[0]["data"]))
+    n = (len(cols[0]["offsets"]) - 1 if cols[0]["dtype"] == "utf8"
+         else len(api.fixed_host(cols[0])) if cols[0]["dtype"] == "dec128"
+         else len(cols[0]["data"]))
     var_idx = [i for i, c in enumerate(cols) if c["dtype"] == "utf8"]
 
     batch = api.DeviceBatch(cols)
@@ -148,8 +150,9 @@ def two_level_partition(cols, key_idx, nparts, buckets=8):
             oc["data"] = api._d2h(final[i]["data"].value, int(boffA[i][-1]), np.uint8)
             oc["lengths"] = api._d2h(final[i]["lengths"].value, n * 4, np.uint32)
         else:
-            oc["data"] = api._d2h(final[i]["data"].value, n * elem[i],
-                                  api.FIXED_NP[c["dtype"]])
+            oc["data"] = api.fixed_out(c["dtype"],
+                                       api._d2h(final[i]["data"].value, n * elem[i],
+                                                api.FIXED_NP[c["dtype"]]))
         if c.get("valid") is not None:
             oc["valid"] = api._d2h(final[i]["valid"].value, n, np.uint8)
         out_cols.append(oc)

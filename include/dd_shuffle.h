@@ -52,7 +52,16 @@ typedef enum dd_dtype {
     DD_DT_F64 = 6,
     DD_DT_BOOL = 7,  /* unpacked u8 0/1 */
     DD_DT_UTF8 = 8,  /* i32 offsets[n+1] + byte buffer */
-    DD_DT_DICT32 = 9 /* i32 indices; dictionary values as utf8 (offsets+bytes) */
+    DD_DT_DICT32 = 9, /* i32 indices; dictionary values as utf8 (offsets+bytes) */
+    /* Opaque 16-byte value in the Arrow Decimal128 value-buffer layout: little-endian
+     * two's complement, lo = bytes 0..7, hi = bytes 8..15. `data` must be 16-byte aligned
+     * (dd_partitioner_create: DD_ERR_INVALID otherwise). Precision and scale are schema,
+     * not device data: the shim keeps them beside the column. Hashes as the two i64 keys
+     * (lo, hi), DESIGN.md §16. Seam: the Decimal128 columns DataFusion gives the TPC-H
+     * money/quantity fields that RepartitionExec(Hash) routes (tests/tpch_plans_test.rs);
+     * arrow's create_hashes over the i128 value buffer is the reference operation.
+     * Interval(MonthDayNano) and FixedSizeBinary(16) share the layout. */
+    DD_DT_DEC128 = 10
 } dd_dtype;
 
 #define DD_MAX_COLS 24
@@ -61,7 +70,7 @@ typedef enum dd_dtype {
 
 typedef struct dd_col_desc {
     int32_t dtype;            /* dd_dtype */
-    const void *data;         /* device: values, or utf8 bytes */
+    const void *data;         /* device: values (DEC128: 16-byte aligned), or utf8 bytes */
     const uint8_t *validity;  /* device, unpacked u8, NULL => all valid */
     const int32_t *offsets;   /* device, UTF8 only: offsets[n_rows+1] */
     int64_t data_len;         /* UTF8: byte length of `data`; else 0 */
@@ -485,6 +494,8 @@ typedef struct dd_ipc_array {
 typedef struct dd_ipc_writer dd_ipc_writer;
 typedef struct dd_ipc_reader dd_ipc_reader;
 
+/* DD_DT_DEC128 fields: DD_ERR_UNSUPPORTED (dd_ipc_field carries no precision and scale;
+ * decimals on the cross-node wire are out of scope). */
 dd_status dd_ipc_writer_create(const dd_ipc_field *fields, int32_t n_fields,
                                int32_t use_lz4, dd_ipc_writer **out);
 dd_status dd_ipc_writer_batch(dd_ipc_writer *w, int64_t n_rows, const dd_ipc_array *cols);
@@ -543,6 +554,7 @@ dd_status dd_partial_reduce_geometry(int64_t n_rows, int32_t *table_slots,
                                      int32_t *probe_limit, int64_t *nblocks,
                                      int64_t *chunk_rows);
 
+/* A DD_DT_DEC128 key or aggregate input: DD_ERR_UNSUPPORTED. */
 dd_status dd_partial_reduce_run(const dd_batch_desc *batch, const int32_t *key_cols,
                                 int32_t n_keys, const int32_t *agg_cols,
                                 const int32_t *agg_ops, int32_t n_aggs, void *stream,
