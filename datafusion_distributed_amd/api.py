@@ -119,6 +119,8 @@ def lib():
         L.dd_bcast_col_offsets.restype = ctypes.c_void_p
         L.dd_reducer_n_rows.restype = ctypes.c_int64
         L.dd_reducer_kernel_ms.restype = ctypes.c_float
+        L.dd_reducer_kernel.restype = ctypes.c_int32
+        L.dd_reducer_waveagg.restype = ctypes.c_int32
         L.dd_dict_gc_n_windows.restype = ctypes.c_uint32
         L.dd_dict_gc_indices.restype = ctypes.c_void_p
         L.dd_dict_gc_dict_offsets.restype = ctypes.c_void_p
@@ -911,11 +913,12 @@ class Exchanged:
 
 
 AGG_OPS = {"sum_f64": 0, "count": 1, "sum_i64": 2, "min_f64": 3, "max_f64": 4,
-           "min_i64": 5, "max_i64": 6}
+           "min_i64": 5, "max_i64": 6, "sum_dec128": 7}
 
 
 def partial_reduce_geometry(n_rows):
-    """Launch geometry partial_reduce uses for an n_rows batch (no device needed):
+    """Launch geometry partial_reduce uses for an n_rows batch whose plan has at most 4
+    aggregates and no sum_dec128 (no device needed):
     {"table_slots", "probe_limit", "nblocks", "chunk_rows"}."""
     slots = ctypes.c_int32()
     probe = ctypes.c_int32()
@@ -928,21 +931,46 @@ def partial_reduce_geometry(n_rows):
             "nblocks": int(nblocks.value), "chunk_rows": int(chunk.value)}
 
 
+def partial_reduce_plan_geometry(n_rows, n_keys, ops):
+    """Launch geometry partial_reduce uses for an n_rows batch under any plan (no device
+    needed). ops: the 1..8 op names of the plan. Returns {"kernel": 0 (at most 4 aggregates,
+    no sum_dec128: the numbers of partial_reduce_geometry) or 1 (the wide kernel),
+    "table_slots", "probe_limit", "block_threads", "lds_bytes", "nblocks", "chunk_rows"}."""
+    na = len(ops)
+    opsc = (ctypes.c_int32 * max(na, 1))(*[AGG_OPS[o] for o in ops])
+    i32 = [ctypes.c_int32() for _ in range(5)]
+    nblocks = ctypes.c_int64()
+    chunk = ctypes.c_int64()
+    _check(lib().dd_partial_reduce_plan_geometry(
+        ctypes.c_int64(n_rows), ctypes.c_int32(n_keys), opsc, ctypes.c_int32(na),
+        *[ctypes.byref(v) for v in i32], ctypes.byref(nblocks), ctypes.byref(chunk)))
+    names = ("kernel", "table_slots", "probe_limit", "block_threads", "lds_bytes")
+    geo = {k: int(v.value) for k, v in zip(names, i32)}
+    geo["nblocks"] = int(nblocks.value)
+    geo["chunk_rows"] = int(chunk.value)
+    return geo
+
+
 def partial_reduce(batch: DeviceBatch, key_idx, aggs):
     """GPU partial aggregation below the shuffle (dd_partial_reduce_run).
 
     key_idx: 1..4 key columns, fixed-width or dict32 (grouped by dictionary index).
-    aggs: 1..4 of (col_index_or_None, op) with op in AGG_OPS: "count" (every row, column
+    aggs: 1..8 of (col_index_or_None, op) with op in AGG_OPS: "count" (every row, column
     ignored), "sum_f64", "sum_i64" (wraps mod 2^64), "min_f64"/"max_f64" (IEEE totalOrder
     on the bit pattern: sign-set NaN < -inf < -0.0 < +0.0 < +inf < sign-clear NaN),
-    "min_i64"/"max_i64". Every op but count skips NULL inputs.
+    "min_i64"/"max_i64", "sum_dec128" (exact sum of a dec128 column, wraps mod 2^128).
+    Every op but count skips NULL inputs.
     Returns {"keys": u64[n, nk] canonical bits (0 for a NULL key component), "keynull":
     u32[n] per-key null bitmask, "aggs": f64[n, na], "nn": u64[n, na] non-null input
-    counts} — integer aggregates (count / sum_i64 / min_i64 / max_i64) are bit-cast in
-    the f64 slots (view with .view(np.int64)). May contain duplicate groups (partial
-    semantics). The final merge sums "nn" per group, skips the value of a partial whose
-    nn is 0 (it holds the op identity), and emits NULL for an aggregate whose total
-    non-null count is 0 (DataFusion semantics).
+    counts, "aggs_hi": u64[n, na], "kernel": 0 or 1, "waveagg": 0 or 1} — integer
+    aggregates (count / sum_i64 / min_i64 / max_i64) are bit-cast in the f64 slots (view
+    with .view(np.int64)); a sum_dec128 has its low 64 bits there (.view(np.uint64)) and
+    its high 64 bits in "aggs_hi", which is 0 for every other op. "kernel" says which
+    kernel ran (partial_reduce_plan_geometry) and "waveagg" the wave-aggregation setting
+    the wide kernel ran with (DD_REDUCE_WAVEAGG; always 0 for kernel 0). May contain
+    duplicate groups (partial semantics). The final merge sums "nn" per group, skips the
+    value of a partial whose nn is 0 (it holds the op identity; (0, 0) for sum_dec128), and
+    emits NULL for an aggregate whose total non-null count is 0 (DataFusion semantics).
     """
     nk = len(key_idx)
     na = len(aggs)
@@ -959,13 +987,29 @@ def partial_reduce(batch: DeviceBatch, key_idx, aggs):
         keynull = np.empty(n, dtype=np.uint32)
         vals = np.empty((n, na), dtype=np.float64)
         nn = np.zeros((n, na), dtype=np.uint64)
+        hi = np.zeros((n, na), dtype=np.uint64)
         if n:
             _check(lib().dd_reducer_fetch(
                 h, keys.ctypes.data_as(ctypes.c_void_p),
                 keynull.ctypes.data_as(ctypes.c_void_p),
                 vals.ctypes.data_as(ctypes.c_void_p)))
             _check(lib().dd_reducer_fetch_nn(h, nn.ctypes.data_as(ctypes.c_void_p)))
+            _check(lib().dd_reducer_fetch_hi(h, hi.ctypes.data_as(ctypes.c_void_p)))
         return {"keys": keys, "keynull": keynull, "aggs": vals, "nn": nn,
-                "kernel_ms": kernel_ms}
+                "aggs_hi": hi, "kernel": int(lib().dd_reducer_kernel(h)),
+                "waveagg": int(lib().dd_reducer_waveagg(h)), "kernel_ms": kernel_ms}
     finally:
         lib().dd_reducer_destroy(h)
+
+
+def reduce_dec128_col(res, g, precision, scale):
+    """The column dict that carries decimal sum `g` of a partial_reduce result into the
+    shuffle: {"dtype": "dec128", "data": u64[n, 2] = [lo, hi], "valid": (nn > 0) as u8, or
+    None when every partial has a non-null input, "precision": min(38, precision + 10)
+    (DataFusion's sum type), "scale": scale}."""
+    lo = np.ascontiguousarray(res["aggs"][:, g]).view(np.uint64)
+    data = np.ascontiguousarray(np.stack([lo, res["aggs_hi"][:, g]], axis=1))
+    ok = res["nn"][:, g] > 0
+    return {"dtype": "dec128", "data": data,
+            "valid": None if ok.all() else ok.astype(np.uint8),
+            "precision": min(38, precision + 10), "scale": scale}

@@ -2167,15 +2167,19 @@ struct dd_reducer {
     uint32_t *keynull = nullptr;
     double *aggs = nullptr;
     uint64_t *nn = nullptr; /* [max_rows][n_aggs] non-null input counts */
+    uint64_t *hi = nullptr; /* wide kernel: [max_rows][n_aggs] high halves of decimal sums */
     uint64_t *n_dev = nullptr;
     int32_t *meta = nullptr; /* device: agg_cols + agg_ops */
     float kernel_ms = 0;     /* hipEvent time of the reduce kernel alone */
+    int32_t kernel = 0;      /* 0 = k_partial_reduce, 1 = k_partial_reduce_wide */
+    int32_t waveagg = 0;     /* the wide kernel's wave-aggregation setting (0 for kernel 0) */
     ~dd_reducer() {
         for (auto &d : dict_hashes) (void)hipFree(d);
         (void)hipFree(keys);
         (void)hipFree(keynull);
         (void)hipFree(aggs);
         (void)hipFree(nn);
+        (void)hipFree(hi);
         (void)hipFree(n_dev);
         (void)hipFree(meta);
     }
@@ -2202,6 +2206,82 @@ extern "C" dd_status dd_partial_reduce_geometry(int64_t n_rows, int32_t *table_s
     return DD_OK;
 }
 
+/* The plan of one partial reduce: which kernel runs it and with what geometry. The one
+ * place the wide kernel's arithmetic lives (used by the run below and reported by
+ * dd_partial_reduce_plan_geometry). */
+struct dd_reduce_plan {
+    int32_t kernel, table_slots, probe_limit, block_threads, lds_bytes;
+    int64_t nblocks, chunk;
+};
+
+static dd_status dd_reduce_make_plan(int64_t n, int32_t n_keys, const int32_t *agg_ops,
+                                     int32_t n_aggs, dd_reduce_plan *p) {
+    if (n_keys < 1 || n_keys > 4) return set_err(DD_ERR_UNSUPPORTED, "1..4 key columns");
+    if (n_aggs < 1)
+        return set_err(DD_ERR_UNSUPPORTED, "partial reduce: at least 1 aggregate");
+    if (n_aggs > DD_RW_MAX_AGGS)
+        return set_err(DD_ERR_UNSUPPORTED, "partial reduce: at most 8 aggregates");
+    int n_dec = 0;
+    for (int g = 0; g < n_aggs; g++) {
+        if (agg_ops[g] < 0 || agg_ops[g] > DD_AGG_SUM_DEC128)
+            return set_err(DD_ERR_INVALID, "unknown aggregate op");
+        if (agg_ops[g] == DD_AGG_SUM_DEC128) n_dec++;
+    }
+    if (n_aggs <= DD_R_NARROW_AGGS && n_dec == 0) {
+        p->kernel = 0;
+        p->table_slots = DD_R_CAP;
+        p->probe_limit = DD_R_PROBE;
+        p->block_threads = 256;
+        /* k_partial_reduce's static tables: hash 8, ready 4, null 4, 4 keys, 4 states, 4 nn */
+        p->lds_bytes = DD_R_CAP * (8 + 4 + 4 + 4 * 8 + 4 * 8 + 4 * 4);
+        dd_reduce_geometry(n, &p->nblocks, &p->chunk);
+        return DD_OK;
+    }
+    /* per slot: hash 8, ready 4, null mask 4, 8 per key, per aggregate 8 state + 4 nn, and
+     * 8 more per decimal sum (its high half) */
+    const int32_t per_slot = 8 + 4 + 4 + 8 * n_keys + 12 * n_aggs + 8 * n_dec;
+    int32_t slots = DD_RW_MAX_SLOTS;
+    while (slots > DD_RW_MIN_SLOTS && (int64_t)slots * per_slot > DD_RW_LDS_LIMIT) slots >>= 1;
+    p->kernel = 1;
+    p->table_slots = slots;
+    p->probe_limit = DD_RW_PROBE;
+    p->block_threads = DD_RW_THREADS;
+    p->lds_bytes = slots * per_slot;
+    int64_t nb = (n + DD_RW_BLOCK_ROWS - 1) / DD_RW_BLOCK_ROWS;
+    if (nb < DD_RW_MIN_BLOCKS) nb = DD_RW_MIN_BLOCKS;
+    if (nb > DD_RW_MAX_BLOCKS) nb = DD_RW_MAX_BLOCKS;
+    p->nblocks = nb;
+    p->chunk = (n + nb - 1) / nb;
+    return DD_OK;
+}
+
+extern "C" dd_status dd_partial_reduce_plan_geometry(
+    int64_t n_rows, int32_t n_keys, const int32_t *agg_ops, int32_t n_aggs, int32_t *kernel,
+    int32_t *table_slots, int32_t *probe_limit, int32_t *block_threads, int32_t *lds_bytes,
+    int64_t *nblocks, int64_t *chunk_rows) {
+    if (n_rows < 0 || !agg_ops || !kernel || !table_slots || !probe_limit || !block_threads ||
+        !lds_bytes || !nblocks || !chunk_rows)
+        return set_err(DD_ERR_INVALID, "null argument or negative row count");
+    dd_reduce_plan p;
+    dd_status st = dd_reduce_make_plan(n_rows, n_keys, agg_ops, n_aggs, &p);
+    if (st != DD_OK) return st;
+    *kernel = p.kernel;
+    *table_slots = p.table_slots;
+    *probe_limit = p.probe_limit;
+    *block_threads = p.block_threads;
+    *lds_bytes = p.lds_bytes;
+    *nblocks = p.nblocks;
+    *chunk_rows = p.chunk;
+    return DD_OK;
+}
+
+/* DD_REDUCE_WAVEAGG=0/1, read per call; unset: the measured default */
+#define DD_RW_WAVEAGG_DEFAULT 0
+static int dd_reduce_waveagg_setting() {
+    if (const char *e = getenv("DD_REDUCE_WAVEAGG")) return atoi(e) == 1;
+    return DD_RW_WAVEAGG_DEFAULT;
+}
+
 extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
                                            const int32_t *key_cols, int32_t n_keys,
                                            const int32_t *agg_cols, const int32_t *agg_ops,
@@ -2210,7 +2290,10 @@ extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
         return set_err(DD_ERR_INVALID, "null argument");
     if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
     if (n_keys < 1 || n_keys > 4) return set_err(DD_ERR_UNSUPPORTED, "1..4 key columns");
-    if (n_aggs < 1 || n_aggs > 4) return set_err(DD_ERR_UNSUPPORTED, "1..4 aggregates");
+    if (n_aggs < 1)
+        return set_err(DD_ERR_UNSUPPORTED, "partial reduce: at least 1 aggregate");
+    if (n_aggs > DD_RW_MAX_AGGS)
+        return set_err(DD_ERR_UNSUPPORTED, "partial reduce: at most 8 aggregates");
     for (int k = 0; k < n_keys; k++) {
         if (key_cols[k] < 0 || key_cols[k] >= batch->n_cols)
             return set_err(DD_ERR_INVALID, "key column out of range");
@@ -2225,9 +2308,15 @@ extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
         if (!agg_cols || agg_cols[g] < 0 || agg_cols[g] >= batch->n_cols)
             return set_err(DD_ERR_INVALID, "agg column out of range");
         int dt = batch->cols[agg_cols[g]].dtype;
+        if (agg_ops[g] == DD_AGG_SUM_DEC128) {
+            if (dt != DD_DT_DEC128)
+                return set_err(DD_ERR_UNSUPPORTED,
+                               "partial reduce: sum_dec128 needs a dec128 column");
+            continue;
+        }
         if (dt == DD_DT_DEC128)
             return set_err(DD_ERR_UNSUPPORTED,
-                           "partial reduce: dec128 aggregate inputs are not supported");
+                           "partial reduce: a dec128 column takes sum_dec128 only");
         if ((agg_ops[g] == DD_AGG_SUM_F64 || agg_ops[g] == DD_AGG_MIN_F64 ||
              agg_ops[g] == DD_AGG_MAX_F64) &&
             dt != DD_DT_F64)
@@ -2239,10 +2328,13 @@ extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
         if (agg_ops[g] < 0 || agg_ops[g] > DD_AGG_MAX_I64)
             return set_err(DD_ERR_INVALID, "unknown aggregate op");
     }
+    const int64_t n = batch->n_rows;
+    dd_reduce_plan plan;
+    if (dd_status st = dd_reduce_make_plan(n, n_keys, agg_ops, n_aggs, &plan)) return st;
+    const bool wide = plan.kernel == 1;
 
     dd_kargs ka;
     memset(&ka, 0, sizeof(ka));
-    const int64_t n = batch->n_rows;
     ka.n_rows = n;
     ka.n_cols = batch->n_cols;
     ka.n_keys = n_keys;
@@ -2257,13 +2349,15 @@ extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
         kc.offsets = cd.offsets;
     }
 
-    int64_t nblocks, chunk;
-    dd_reduce_geometry(n, &nblocks, &chunk);
-    const int64_t max_rows = n + nblocks * DD_R_CAP + 1; /* spill worst case + table flush */
+    const int64_t nblocks = plan.nblocks, chunk = plan.chunk;
+    /* spill worst case + table flush */
+    const int64_t max_rows = n + nblocks * plan.table_slots + 1;
 
     auto r = new dd_reducer();
     r->n_keys = n_keys;
     r->n_aggs = n_aggs;
+    r->kernel = plan.kernel;
+    r->waveagg = wide ? dd_reduce_waveagg_setting() : 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     auto fail = [&](const char *m) {
         if (e0) (void)hipEventDestroy(e0);
@@ -2289,24 +2383,35 @@ extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
         hipMalloc((void **)&r->aggs, (size_t)max_rows * n_aggs * 8) != hipSuccess ||
         hipMalloc((void **)&r->nn, (size_t)max_rows * n_aggs * 8) != hipSuccess ||
         hipMalloc((void **)&r->n_dev, 8) != hipSuccess ||
-        hipMalloc((void **)&r->meta, 2 * 4 * 4) != hipSuccess)
+        hipMalloc((void **)&r->meta, 2 * DD_RW_MAX_AGGS * 4) != hipSuccess)
+        return fail("partial reduce alloc");
+    if (wide && hipMalloc((void **)&r->hi, (size_t)max_rows * n_aggs * 8) != hipSuccess)
         return fail("partial reduce alloc");
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(r->n_dev, 0, 8, s) != hipSuccess) return fail("memset");
-    int32_t meta_h[8] = {};
+    /* agg_cols then agg_ops, each padded to the running kernel's aggregate cap */
+    const int cap = wide ? DD_RW_MAX_AGGS : DD_R_NARROW_AGGS;
+    int32_t meta_h[2 * DD_RW_MAX_AGGS] = {};
     for (int g = 0; g < n_aggs; g++) {
         meta_h[g] = agg_cols ? agg_cols[g] : 0;
-        meta_h[4 + g] = agg_ops[g];
+        meta_h[cap + g] = agg_ops[g];
     }
-    if (hipMemcpyAsync(r->meta, meta_h, sizeof(meta_h), hipMemcpyHostToDevice, s) !=
+    if (hipMemcpyAsync(r->meta, meta_h, (size_t)2 * cap * 4, hipMemcpyHostToDevice, s) !=
         hipSuccess)
         return fail("meta upload");
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, s);
-    hipError_t e = dd_launch_partial_reduce(&ka, nblocks, chunk, n_aggs, r->meta,
-                                            r->meta + 4, r->keys, r->keynull, r->aggs,
-                                            r->nn, r->n_dev, s);
+    hipError_t e;
+    if (wide)
+        e = dd_launch_partial_reduce_wide(&ka, r->waveagg, nblocks, chunk, n_aggs,
+                                          plan.table_slots, plan.probe_limit,
+                                          (size_t)plan.lds_bytes, r->meta, r->meta + cap,
+                                          r->keys, r->keynull, (uint64_t *)r->aggs, r->hi,
+                                          r->nn, r->n_dev, s);
+    else
+        e = dd_launch_partial_reduce(&ka, nblocks, chunk, n_aggs, r->meta, r->meta + cap,
+                                     r->keys, r->keynull, r->aggs, r->nn, r->n_dev, s);
     (void)hipEventRecord(e1, s);
     if (e != hipSuccess) return fail(hipGetErrorString(e));
     if (hipStreamSynchronize(s) != hipSuccess) return fail("sync");
@@ -2344,6 +2449,20 @@ extern "C" dd_status dd_reducer_fetch_nn(const dd_reducer *r, uint64_t *host_nn)
                       hipMemcpyDeviceToHost));
     return DD_OK;
 }
+
+/* host_hi[n_rows][n_aggs]: the high 64 bits of each decimal sum, 0 for every other op */
+extern "C" dd_status dd_reducer_fetch_hi(const dd_reducer *r, uint64_t *host_hi) {
+    const size_t bytes = (size_t)r->n_rows * r->n_aggs * 8;
+    if (!r->hi) { /* k_partial_reduce ran: no decimal sum in the plan */
+        memset(host_hi, 0, bytes);
+        return DD_OK;
+    }
+    HIP_TRY(hipMemcpy(host_hi, r->hi, bytes, hipMemcpyDeviceToHost));
+    return DD_OK;
+}
+
+extern "C" int32_t dd_reducer_kernel(const dd_reducer *r) { return r->kernel; }
+extern "C" int32_t dd_reducer_waveagg(const dd_reducer *r) { return r->waveagg; }
 
 extern "C" void dd_reducer_destroy(dd_reducer *r) { delete r; }
 

@@ -22,6 +22,21 @@
 #define DD_R_MIN_BLOCKS 8
 #define DD_R_MAX_BLOCKS 1024
 
+/* wide partial reduce (k_partial_reduce_wide): up to DD_RW_MAX_AGGS
+ * aggregates, exact dec128 sums; the table lives in dynamic LDS sized per plan and is
+ * reported by dd_partial_reduce_plan_geometry */
+#define DD_R_NARROW_AGGS 4    /* k_partial_reduce's aggregate cap */
+#define DD_RW_MAX_AGGS 8
+#define DD_RW_THREADS 1024    /* one table serves 16 waves */
+#define DD_RW_MAX_SLOTS 1024  /* table slots: a power of two in [MIN, MAX] */
+#define DD_RW_MIN_SLOTS 512
+#define DD_RW_PROBE 64
+#define DD_RW_LDS_LIMIT 163840 /* LDS one workgroup may hold on gfx950 */
+#define DD_RW_BLOCK_ROWS 8192  /* target rows per block: 8 per thread */
+#define DD_RW_MIN_BLOCKS 8
+#define DD_RW_MAX_BLOCKS 2048
+#define DD_RW_PEEL_MIN 8       /* wave aggregation: smallest lane group worth a reduce */
+
 /* dtype codes mirror dd_dtype in include/dd_shuffle.h */
 enum {
     DD_KDT_U8 = 1,
@@ -249,6 +264,15 @@ hipError_t dd_launch_partial_reduce(const dd_kargs *a, int64_t nblocks, int64_t 
                                     const int32_t *agg_ops, uint64_t *out_keys,
                                     uint32_t *out_keynull, double *out_aggs,
                                     uint64_t *out_nn, uint64_t *out_n, hipStream_t s);
+/* agg_cols / agg_ops: DD_RW_MAX_AGGS device ints each; lds_bytes as the plan geometry
+ * reports it (sets the kernel's dynamic-LDS attribute when past 64 KiB) */
+hipError_t dd_launch_partial_reduce_wide(const dd_kargs *a, int waveagg, int64_t nblocks,
+                                         int64_t chunk_rows, int n_aggs, int table_slots,
+                                         int probe_limit, size_t lds_bytes,
+                                         const int32_t *agg_cols, const int32_t *agg_ops,
+                                         uint64_t *out_keys, uint32_t *out_keynull,
+                                         uint64_t *out_aggs, uint64_t *out_hi,
+                                         uint64_t *out_nn, uint64_t *out_n, hipStream_t s);
 }
 
 #endif

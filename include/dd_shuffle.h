@@ -523,7 +523,7 @@ void dd_ipc_reader_destroy(dd_ipc_reader *r);
  * i32, i64, f32, f64, bool) or dict32 grouped BY INDEX (utf8 keys are unsupported). Float
  * keys are canonicalised like the row hash (-0.0 -> +0.0, every NaN -> one quiet NaN).
  * Duplicate dictionary values under different indices yield separate partial groups,
- * which the final aggregate merges by value. Up to 4 aggregates, ops below.
+ * which the final aggregate merges by value. Up to 8 aggregates, ops below.
  *
  * Aggregate contract (every op but COUNT skips NULL inputs):
  *  - Each output row carries, per aggregate, the NON-NULL INPUT COUNT `nn`
@@ -535,7 +535,16 @@ void dd_ipc_reader_destroy(dd_ipc_reader *r);
  *    -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN. A sign-set NaN (e.g. the
  *    0xfff8... that x86 produces for inf - inf) therefore sorts BELOW -inf; only a
  *    sign-clear NaN sorts above +inf. NaN payloads and the sign of zero are preserved.
- *  - SUM_F64 adds in an unspecified order (floating-point atomics). */
+ *  - SUM_F64 adds in an unspecified order (floating-point atomics).
+ *  - SUM_DEC128 sums a DD_DT_DEC128 column exactly: the state is a 128-bit
+ *    two's-complement sum that wraps modulo 2^128, low half in the value slot (bit-cast,
+ *    like the integer ops), high half from dd_reducer_fetch_hi. A partial with nn == 0
+ *    holds (0, 0). Precision and scale are schema: the result type
+ *    Decimal128(min(38, p + 10), s) is the caller's business. avg(dec128) is this op plus
+ *    its nn; there is no separate avg op.
+ *  - Not offered: min / max of a dec128 column. gfx950 has no 128-bit LDS atomic, and a
+ *    per-slot lock is a hang risk on hardware without independent thread scheduling (the
+ *    reason the probe loop never spins). dec128 keys are not offered either. */
 
 typedef struct dd_reducer dd_reducer;
 
@@ -546,15 +555,32 @@ typedef struct dd_reducer dd_reducer;
 #define DD_AGG_MAX_F64 4
 #define DD_AGG_MIN_I64 5 /* signed min / max of an i64 column */
 #define DD_AGG_MAX_I64 6
+#define DD_AGG_SUM_DEC128 7 /* exact wrapping 128-bit sum of a dec128 column */
 
-/* Launch geometry dd_partial_reduce_run uses for an n_rows batch: LDS table slots per
- * block, probe limit before a row spills as a singleton group, block count and rows per
- * block (the last block may be ragged or empty). Needs no device. */
+/* Launch geometry dd_partial_reduce_run uses for an n_rows batch whose plan has at most 4
+ * aggregates and no SUM_DEC128: LDS table slots per block, probe limit before a row
+ * spills as a singleton group, block count and rows per block (the last block may be
+ * ragged or empty). Needs no device. */
 dd_status dd_partial_reduce_geometry(int64_t n_rows, int32_t *table_slots,
                                      int32_t *probe_limit, int64_t *nblocks,
                                      int64_t *chunk_rows);
 
-/* A DD_DT_DEC128 key or aggregate input: DD_ERR_UNSUPPORTED. */
+/* The same for any plan (n_keys 1..4, agg_ops[n_aggs] with n_aggs 1..8). kernel: 0 = the
+ * 4-aggregate kernel (at most 4 aggregates, none of them SUM_DEC128; the numbers are those
+ * of dd_partial_reduce_geometry), 1 = the wide kernel, whose table is sized for the plan:
+ * table_slots is a power of two in [512, 1024] and lds_bytes <= 163840. The home slot of
+ * a row is max(row hash, 1) % table_slots in both. Needs no device. */
+dd_status dd_partial_reduce_plan_geometry(int64_t n_rows, int32_t n_keys,
+                                          const int32_t *agg_ops, int32_t n_aggs,
+                                          int32_t *kernel, int32_t *table_slots,
+                                          int32_t *probe_limit, int32_t *block_threads,
+                                          int32_t *lds_bytes, int64_t *nblocks,
+                                          int64_t *chunk_rows);
+
+/* 1..8 aggregates. DD_ERR_UNSUPPORTED, with a message that names the cause, for: a
+ * DD_DT_DEC128 key; any op but SUM_DEC128 on a DD_DT_DEC128 column; SUM_DEC128 on any
+ * other column; more than 8 aggregates. The wide kernel's wave aggregation is chosen by
+ * DD_REDUCE_WAVEAGG=0/1, read per call. */
 dd_status dd_partial_reduce_run(const dd_batch_desc *batch, const int32_t *key_cols,
                                 int32_t n_keys, const int32_t *agg_cols,
                                 const int32_t *agg_ops, int32_t n_aggs, void *stream,
@@ -569,6 +595,13 @@ dd_status dd_reducer_fetch(const dd_reducer *r, uint64_t *host_keys, uint32_t *h
  * emits NULL when the total is 0 (DataFusion: SUM/MIN/MAX over an all-null group is NULL,
  * not the op identity; COUNT counts rows and is never NULL) */
 dd_status dd_reducer_fetch_nn(const dd_reducer *r, uint64_t *host_nn);
+/* host_hi[n][n_aggs]: the high 64 bits of each SUM_DEC128 slot (host_aggs holds the low
+ * 64), 0 for every other op */
+dd_status dd_reducer_fetch_hi(const dd_reducer *r, uint64_t *host_hi);
+/* which kernel ran (as dd_partial_reduce_plan_geometry names them) and the wave-aggregation
+ * setting it ran with (0 or 1; always 0 for kernel 0) */
+int32_t dd_reducer_kernel(const dd_reducer *r);
+int32_t dd_reducer_waveagg(const dd_reducer *r);
 void dd_reducer_destroy(dd_reducer *r);
 
 /* ---------------- device helpers (harness convenience; not part of the seam) ------- */
