@@ -529,6 +529,15 @@ class Partitioner:
             self.h, col, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return out
 
+    def var_offsets64(self, col):
+        """Download the rebuilt Arrow offsets u64[n_rows+1] of utf8 column `col` in
+        partition-major order, zero-based (dd_partitioner_var_offsets64, the K4c output), or
+        None on the v1 path, which keeps lengths only (tests only)."""
+        p = lib().dd_partitioner_var_offsets64(self.h, ctypes.c_int32(col))
+        if not p:
+            return None
+        return _d2h(p, (self.batch.n_rows + 1) * 8, np.uint64)
+
     def kernel_ms(self):
         out = (ctypes.c_float * 3)()
         _check(lib().dd_partitioner_kernel_ms(self.h, out))

@@ -701,6 +701,8 @@ extern "C" dd_status dd_partitioner_create(const dd_batch_desc *batch, const int
                     }
                     const int64_t R5 = (int64_t)wpb5 * 64;
                     const size_t img = (size_t)R5 * maxlen + 8;
+                    /* k5_scatter's whole LDS: it declares no static __shared__ beside
+                     * this dynamic carve, so the gate below is the launch limit */
                     const size_t lds5 =
                         (size_t)wpb5 * P * 4 + (size_t)(P + 1) * 4 + img;
                     if (mok && maxlen > 0 && maxlen <= 128 && lds5 <= 163840) {
@@ -904,7 +906,7 @@ extern "C" dd_status dd_partitioner_run_phase2(dd_partitioner *p, void *stream) 
             const dd_col_desc &cd = p->batch.cols[ci];
             HIP_TRY(dd_launch_var_bytes(
                 p->out_lengths[ci], p->src_row, cd.offsets, (const uint8_t *)cd.data,
-                p->ka.n_rows, cd.data_len, p->k4_partials, p->out_off[v],
+                p->ka.n_rows, p->k4_partials, p->out_off[v],
                 (uint8_t *)p->out_data[ci], p->part_offsets, p->nparts,
                 p->part_boffsets + (size_t)v * (p->nparts + 1), p->k4w_meta,
                 p->k4w_order, p->k5 ? 1 : 0, s));

@@ -254,7 +254,7 @@ hipError_t dd_launch_off64_to_off32(const uint64_t *off64, int64_t lo, int64_t n
                                     int32_t *out32, hipStream_t s);
 hipError_t dd_launch_var_bytes(const uint32_t *lens, const uint32_t *src_row,
                                const int32_t *in_offsets, const uint8_t *in_bytes,
-                               int64_t n, int64_t total_bytes, uint64_t *partials,
+                               int64_t n, uint64_t *partials,
                                uint64_t *out_off, uint8_t *out_bytes,
                                const uint64_t *part_offsets, uint32_t nparts,
                                uint64_t *part_boffsets, uint32_t *k4w_meta,

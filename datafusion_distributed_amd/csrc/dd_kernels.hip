@@ -2352,8 +2352,6 @@ __global__ __launch_bounds__(WPB5 * WAVE) void k5_scatter(
     uint32_t *gb = gb_all + (size_t)wid * nparts;
     uint32_t *gb0 = gb_all;
     const uint64_t lt = ((uint64_t)1 << lane) - 1;
-    __shared__ uint32_t lens_s[WPB5][WAVE];
-    __shared__ uint32_t srcb_s[WPB5][WAVE];
 
     const int64_t r = blockIdx.x;
     if (r >= nrounds) return;
@@ -2377,22 +2375,20 @@ __global__ __launch_bounds__(WPB5 * WAVE) void k5_scatter(
         sb = (uint32_t)o0;
         pidv = pid[row];
     }
-    lens_s[wid][lane] = len;
-    srcb_s[wid][lane] = sb;
-    /* group byte prefix among same-partition lanes (v1 k_scatter idiom) */
+    /* group byte prefix among same-partition lanes. A length fits 8 bits (the create-time
+     * gate admits maxlen <= 128), so one ballot per bit hands every lane the lengths of
+     * the whole wave in registers: the kernel keeps no LDS beside the dynamic carve, which
+     * is what the gate budgets (dd_host.cpp). */
     const uint64_t act = __ballot(row < n);
+    uint64_t lbit[8];
+#pragma unroll
+    for (int b = 0; b < 8; b++) lbit[b] = __ballot((len >> b) & 1u);
     if (row < n) {
-        uint64_t eq = dd_eq_mask(pidv, act, nbits);
-        uint32_t bpre = 0, bsum = 0;
-        uint64_t m = eq;
-        while (m) {
-            int j = __ffsll((unsigned long long)m) - 1;
-            uint32_t lj = lens_s[wid][j];
-            if (j < lane) bpre += lj;
-            bsum += lj;
-            m &= m - 1;
-        }
-        (void)bsum;
+        const uint64_t below = dd_eq_mask(pidv, act, nbits) & lt;
+        uint32_t bpre = 0;
+#pragma unroll
+        for (int b = 0; b < 8; b++)
+            bpre += (uint32_t)__popcll((unsigned long long)(below & lbit[b])) << b;
         if (len) {
             const uint32_t gdst = gb[pidv] + bpre;       /* global byte pos */
             const uint32_t slot = roff[pidv] + (gdst - gb0[pidv]); /* image byte pos */
@@ -2464,8 +2460,8 @@ __global__ void k4_len_partials(const uint32_t *lens, int64_t n, uint64_t *parti
     if (lane == 0) partials[w] = s;
 }
 
-__global__ void k4_scan_partials(uint64_t *partials, int nranges, int64_t total_bytes,
-                                 uint64_t *out_off, int64_t n) {
+__global__ void k4_scan_partials(uint64_t *partials, int nranges, uint64_t *out_off,
+                                 int64_t n) {
     /* 256 threads: span sums -> one-wave shfl scan -> span rewrite */
     __shared__ uint64_t tmp[256];
     const int tid = threadIdx.x;
@@ -2496,7 +2492,9 @@ __global__ void k4_scan_partials(uint64_t *partials, int nranges, int64_t total_
         partials[i] = run;
         run += v;
     }
-    if (tid == 0) out_off[n] = (uint64_t)total_bytes;
+    /* the scanned total, not the input buffer's data_len: a sliced column's buffer is
+     * longer than its strings (dd_shuffle.h, dd_col_desc) */
+    if (tid == 0) out_off[n] = tmp[255];
 }
 
 __global__ void k4_off_rewrite(const uint32_t *lens, int64_t n, const uint64_t *partials,
@@ -2607,16 +2605,13 @@ __global__ void k_off64_to_off32(const uint64_t *off64, int64_t lo, int64_t n,
 }
 
 __global__ void k4_part_boffsets(const uint64_t *out_off, const uint64_t *part_offsets,
-                                 uint32_t nparts, int64_t n, int64_t total_bytes,
-                                 uint64_t *part_boffsets) {
+                                 uint32_t nparts, int64_t n, uint64_t *part_boffsets) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p > nparts) return;
-    if (p == nparts) {
-        part_boffsets[p] = (uint64_t)total_bytes;
-        return;
-    }
+    /* part_offsets[P] == n, as is every trailing empty partition's: out_off[n] is the
+     * byte total */
     const int64_t s = (int64_t)part_offsets[p];
-    part_boffsets[p] = (s < n) ? out_off[s] : (uint64_t)total_bytes;
+    part_boffsets[p] = out_off[s < n ? s : n];
 }
 
 /* ---------------- launchers (called from dd_host.cpp) ---------------- */
@@ -2652,7 +2647,7 @@ hipError_t dd_launch_off64_to_off32(const uint64_t *off64, int64_t lo, int64_t n
 
 hipError_t dd_launch_var_bytes(const uint32_t *lens, const uint32_t *src_row,
                                const int32_t *in_offsets, const uint8_t *in_bytes,
-                               int64_t n, int64_t total_bytes, uint64_t *partials,
+                               int64_t n, uint64_t *partials,
                                uint64_t *out_off, uint8_t *out_bytes,
                                const uint64_t *part_offsets, uint32_t nparts,
                                uint64_t *part_boffsets, uint32_t *k4w_meta,
@@ -2660,7 +2655,7 @@ hipError_t dd_launch_var_bytes(const uint32_t *lens, const uint32_t *src_row,
     const int wavegrid = K4_RANGES * WAVE / 256;
     hipLaunchKernelGGL(k4_len_partials, dim3(wavegrid), dim3(256), 0, s, lens, n, partials);
     hipLaunchKernelGGL(k4_scan_partials, dim3(1), dim3(256), 0, s, partials, K4_RANGES,
-                       total_bytes, out_off, n);
+                       out_off, n);
     hipLaunchKernelGGL(k4_off_rewrite, dim3(wavegrid), dim3(256), 0, s, lens, n, partials,
                        out_off);
     /* Slot-order gather (k4_copy). MEASURED NEGATIVES (kept out of the tree, see
@@ -2686,9 +2681,8 @@ hipError_t dd_launch_var_bytes(const uint32_t *lens, const uint32_t *src_row,
     }
     (void)k4w_meta;
     (void)k4w_order;
-    (void)total_bytes;
     hipLaunchKernelGGL(k4_part_boffsets, dim3((nparts + 256) / 256 + 1), dim3(256), 0, s,
-                       out_off, part_offsets, nparts, n, total_bytes, part_boffsets);
+                       out_off, part_offsets, nparts, n, part_boffsets);
     return hipGetLastError();
 }
 

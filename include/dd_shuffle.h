@@ -78,6 +78,15 @@ typedef struct dd_col_desc {
     const int32_t *dict_offsets; /* DICT32: device offsets[dict_n+1] */
     int64_t dict_n;           /* DICT32: number of dictionary values */
 } dd_col_desc;
+/* UTF8 input to dd_partitioner_create may be an Arrow slice: offsets[0] may be non-zero and
+ * `data` may hold bytes before offsets[0] and after offsets[n_rows]; the one requirement is
+ * data_len >= offsets[n_rows] (all of `data` stays readable). Row i's bytes are
+ * data[offsets[i] .. offsets[i+1]). Outputs are zero-based whatever the input's base: the
+ * column's output buffer has data_len bytes, of which the first offsets[n_rows] - offsets[0]
+ * are defined (the strings in partition-major order) and the rest unspecified;
+ * dd_partitioner_byte_offsets[P] and dd_partitioner_var_offsets64[n_rows] equal that byte
+ * total, not data_len. The reuse contract below is narrower: a refilled column is zero-based
+ * and exactly sized. */
 
 typedef struct dd_batch_desc {
     int64_t n_rows;

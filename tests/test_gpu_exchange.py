@@ -15,13 +15,14 @@ pytestmark = pytest.mark.gpu
 def test_self_exchange_roundtrip():
     rng = np.random.default_rng(31)
     n, P = 100000, 16
-    rows = [b"s" * int(l) for l in rng.integers(0, 20, n)]
     off = np.zeros(n + 1, dtype=np.int32)
-    off[1:] = np.cumsum([len(r) for r in rows])
+    off[1:] = np.cumsum(rng.integers(0, 20, n))
+    # random bytes: a byte moved to the wrong place must differ from the one it replaces
+    data = np.random.default_rng(310).integers(33, 127, int(off[-1]), dtype=np.int64)
     cols = [
         {"dtype": "i64", "data": rng.integers(0, 10**12, n, dtype=np.int64), "valid": None},
         {"dtype": "f64", "data": rng.normal(size=n), "valid": None},
-        {"dtype": "utf8", "data": np.frombuffer(b"".join(rows), dtype=np.uint8),
+        {"dtype": "utf8", "data": data.astype(np.uint8),
          "offsets": off, "valid": (rng.random(n) > 0.1).astype(np.uint8)},
     ]
     batch = api.DeviceBatch(cols)

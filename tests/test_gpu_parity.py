@@ -40,7 +40,12 @@ def compare_to_oracle(part, cols, key_idx, nparts, ref=None):
         exp = ref["cols"][i]
         if col["dtype"] == "utf8":
             assert (got["lengths"] == exp["lengths"]).all(), f"col {i} lengths differ"
-            assert got["data"].tobytes() == exp["data"].tobytes(), f"col {i} bytes differ"
+            # the output buffer is as long as the input's (data_len); its first
+            # offsets[n] - offsets[0] bytes are defined, whatever follows them is not
+            assert len(got["data"]) == np.asarray(col["data"], dtype=np.uint8).nbytes
+            total = len(exp["data"])
+            assert got["data"][:total].tobytes() == exp["data"].tobytes(), \
+                f"col {i} bytes differ"
             # byte offsets = prefix of lengths at partition boundaries
             boff = part.byte_offsets(i)
             lens64 = exp["lengths"].astype(np.int64)
@@ -48,7 +53,14 @@ def compare_to_oracle(part, cols, key_idx, nparts, ref=None):
             if n:
                 pref[1:] = np.cumsum(lens64)
             expected_boff = pref[ref["part_offsets"]]
-            assert (boff == expected_boff).all(), f"col {i} byte offsets differ"
+            assert (boff == expected_boff).all(), \
+                f"col {i} byte offsets differ: {boff} vs {expected_boff}"
+            # staged engines also rebuild the Arrow offsets of the partition-major output
+            off64 = part.var_offsets64(i)
+            if off64 is not None:
+                assert off64.shape == (n + 1,)
+                assert (off64.astype(np.int64) == pref).all(), \
+                    f"col {i} var_offsets64 differ (last: {off64[-1]} vs {pref[-1]})"
         elif col["dtype"] in ("f32", "f64"):
             assert np.array_equal(got["data"], exp["data"], equal_nan=True), \
                 f"col {i} data differ"
@@ -126,12 +138,13 @@ def test_gpu_skew_zipf_utf8_payload():
     rng = np.random.default_rng(9)
     n = 200000
     keys = rng.zipf(1.1, n).astype(np.int64) % 100000
-    rows = [b"u" * int(l) for l in rng.integers(0, 32, n)]
     off = np.zeros(n + 1, dtype=np.int32)
-    off[1:] = np.cumsum([len(r) for r in rows])
+    off[1:] = np.cumsum(rng.integers(0, 32, n))
+    # random bytes: a byte moved to the wrong place must differ from the one it replaces
+    data = np.random.default_rng(90).integers(33, 127, int(off[-1]), dtype=np.int64)
     cols = [
         {"dtype": "i64", "data": keys, "valid": None},
-        {"dtype": "utf8", "data": np.frombuffer(b"".join(rows), dtype=np.uint8),
+        {"dtype": "utf8", "data": data.astype(np.uint8),
          "offsets": off, "valid": (rng.random(n) > 0.1).astype(np.uint8)},
     ]
     check_against_oracle(cols, [0], 128)

@@ -58,6 +58,42 @@ def test_c_matches_pyref_fresh_random():
                         assert (a[k] == b[k]).all()
 
 
+@pytest.mark.parametrize("key_idx", [[0], [1], [1, 0]], ids=["payload", "key", "two-keys"])
+@pytest.mark.parametrize("base,slack", [(37, 53), (37, 0), (0, 53)])
+def test_c_matches_pyref_sliced_utf8(base, slack, key_idx):
+    """A utf8 column as an Arrow slice hands it over: offsets[0] = base > 0 and `slack`
+    bytes behind the last string. As payload, as sole key and as one of two keys both
+    restatements give the same pids, order, offsets, lengths and bytes; the outputs are
+    zero-based and hold none of the bytes around the strings."""
+    from tests.test_gpu_var_bytes import FILL, utf8_col
+
+    rng = np.random.default_rng([base, slack])
+    n = 3000
+    lens = rng.integers(0, 18, n)
+    valid = (rng.random(n) > 0.2).astype(np.uint8)
+    col = utf8_col(lens, base, slack, rng=rng, valid=valid)
+    assert col["offsets"][0] == base and len(col["data"]) == base + lens.sum() + slack
+    cols = [{"dtype": "i64", "data": rng.integers(0, 10**12, n, dtype=np.int64),
+             "valid": None}, col]
+    rc = oracle.repartition(cols, key_idx, 16)
+    rp = pyref.repartition(cols, key_idx, 16)
+    for name in ("hash", "pid", "order", "part_offsets"):
+        assert (rc[name] == rp[name]).all(), name
+    for a, b in zip(rc["cols"], rp["cols"]):
+        for k in ("data", "lengths", "valid"):
+            if k in a:
+                assert a[k].shape == b[k].shape and (a[k] == b[k]).all(), k
+    out = rc["cols"][1]
+    assert (out["lengths"] == lens[rc["order"]]).all()
+    assert len(out["data"]) == lens.sum() and not (out["data"] == FILL).any()
+    # the same strings zero-based with an exact buffer partition identically
+    flat = utf8_col(lens, rng=np.random.default_rng(0), valid=valid)
+    flat["data"] = col["data"][base:base + int(lens.sum())]
+    rf = oracle.repartition([cols[0], flat], key_idx, 16)
+    assert (rf["order"] == rc["order"]).all()
+    assert rf["cols"][1]["data"].tobytes() == out["data"].tobytes()
+
+
 def test_empty_batch():
     """Zero-row batches must round-trip (the reference tests zero-column/empty batches over
     the wire: tests/empty_columns_between_workers.rs:11-31)."""
