@@ -121,6 +121,9 @@ def lib():
         L.dd_reducer_kernel_ms.restype = ctypes.c_float
         L.dd_reducer_kernel.restype = ctypes.c_int32
         L.dd_reducer_waveagg.restype = ctypes.c_int32
+        L.dd_finalizer_n_groups.restype = ctypes.c_int64
+        L.dd_finalizer_destroy.restype = None
+        L.dd_finalizer_destroy.argtypes = [ctypes.c_void_p]
         L.dd_dict_gc_n_windows.restype = ctypes.c_uint32
         L.dd_dict_gc_indices.restype = ctypes.c_void_p
         L.dd_dict_gc_dict_offsets.restype = ctypes.c_void_p
@@ -1022,3 +1025,105 @@ def reduce_dec128_col(res, g, precision, scale):
     return {"dtype": "dec128", "data": data,
             "valid": None if ok.all() else ok.astype(np.uint8),
             "precision": min(38, precision + 10), "scale": scale}
+
+
+def final_merge(batch: DeviceBatch, key_idx, aggs, seg_offsets=None, seg_part=None, n_parts=1):
+    """GPU final aggregation above the shuffle (dd_final_merge_run): merge the
+    partial states in `batch` to one row per (partition, group).
+
+    key_idx: 1..4 fixed-width key columns (u8, bool, i16, i32, i64, f32, f64), nullable.
+    aggs: 1..8 of (state_col, op, nn_col) with op in AGG_OPS read as a merge op; nn_col is
+    the i64 column of non-null input counts, None (or -1) for "count", whose state column
+    holds the partial counts and whose nn is the merged count. A partial with nn == 0 is
+    skipped; a total nn of 0 means SQL NULL (value slot unspecified).
+    seg_offsets i64[S + 1], seg_part i32[S], n_parts: the segment layout; rows of all
+    segments with one partition id form a partition and groups are formed within it.
+    Default: one segment, one partition (a global group-by). exchanged_batch and
+    partitioned_batch return (batch, layout) with layout a dict of these three, so
+    final_merge(batch, key_idx, aggs, **layout) merges a shuffle's output in place.
+    Returns {"keys": u64[n, nk], "keynull": u32[n], "aggs": f64[n, na] (integers bit-cast,
+    min / max as value bits, a sum_dec128's low half), "aggs_hi": u64[n, na], "nn":
+    u64[n, na], "group_offsets": i64[n_parts + 1] (partition p's groups are rows
+    [off[p], off[p + 1]); their order inside a partition is unspecified), "kernel_ms":
+    [claim, scan, merge]}."""
+    nk = len(key_idx)
+    na = len(aggs)
+    if seg_offsets is None:
+        seg_offsets, seg_part, n_parts = [0, batch.n_rows], [0], 1
+    off = np.ascontiguousarray(seg_offsets, dtype=np.int64)
+    part = np.ascontiguousarray(seg_part, dtype=np.int32)
+    if len(off) != len(part) + 1:
+        raise ValueError("final_merge: seg_offsets must have one entry more than seg_part")
+    keysc = (ctypes.c_int32 * max(nk, 1))(*key_idx)
+    statec = (ctypes.c_int32 * max(na, 1))(*[c for c, _, _ in aggs])
+    opsc = (ctypes.c_int32 * max(na, 1))(*[AGG_OPS[o] for _, o, _ in aggs])
+    nnc = (ctypes.c_int32 * max(na, 1))(*[-1 if c is None else c for _, _, c in aggs])
+    h = ctypes.c_void_p()
+    _check(lib().dd_final_merge_run(
+        ctypes.byref(batch.desc), keysc, nk, statec, opsc, nnc, na,
+        off.ctypes.data_as(ctypes.c_void_p), part.ctypes.data_as(ctypes.c_void_p),
+        ctypes.c_int32(len(part)), ctypes.c_int32(n_parts), None, ctypes.byref(h)))
+    try:
+        n = int(lib().dd_finalizer_n_groups(h))
+        keys = np.zeros((n, nk), dtype=np.uint64)
+        keynull = np.zeros(n, dtype=np.uint32)
+        vals = np.zeros((n, na), dtype=np.float64)
+        nn = np.zeros((n, na), dtype=np.uint64)
+        hi = np.zeros((n, na), dtype=np.uint64)
+        goff = np.zeros(n_parts + 1, dtype=np.int64)
+        ms = (ctypes.c_float * 3)()
+        _check(lib().dd_finalizer_group_offsets(h, goff.ctypes.data_as(ctypes.c_void_p)))
+        _check(lib().dd_finalizer_kernel_ms(h, ms))
+        if n:
+            _check(lib().dd_finalizer_fetch(
+                h, keys.ctypes.data_as(ctypes.c_void_p),
+                keynull.ctypes.data_as(ctypes.c_void_p),
+                vals.ctypes.data_as(ctypes.c_void_p)))
+            _check(lib().dd_finalizer_fetch_nn(h, nn.ctypes.data_as(ctypes.c_void_p)))
+            _check(lib().dd_finalizer_fetch_hi(h, hi.ctypes.data_as(ctypes.c_void_p)))
+        return {"keys": keys, "keynull": keynull, "aggs": vals, "aggs_hi": hi, "nn": nn,
+                "group_offsets": goff, "kernel_ms": list(ms)}
+    finally:
+        lib().dd_finalizer_destroy(h)
+
+
+def _output_view(src, col_data, col_validity, n_rows):
+    """Non-owning DeviceBatch over the fixed-width output columns of a run Partitioner or
+    an Exchanged (whose buffers must outlive it)."""
+    view_cols = []
+    for i, col in enumerate(src.cols):
+        if col["dtype"] not in ELEM_SIZE:
+            raise ValueError(f"column {i}: a {col['dtype']} column has no fixed-width device "
+                             "view (final_merge takes fixed-width columns)")
+        view_cols.append({"dtype": col["dtype"], "data_ptr": col_data(i),
+                          "valid_ptr": col_validity(i)})
+    return DeviceBatch.from_device(view_cols, n_rows)
+
+
+def partitioned_batch(part: Partitioner):
+    """(batch, layout) of a run Partitioner's output: a non-owning device view
+    (DeviceBatch.from_device) plus {"seg_offsets", "seg_part", "n_parts"}, one segment per
+    partition. Nothing is copied; `part` must outlive the view."""
+    L = lib()
+    batch = _output_view(part.batch, lambda i: L.dd_partitioner_col_data(part.h, i),
+                         lambda i: L.dd_partitioner_col_validity(part.h, i),
+                         part.batch.n_rows)
+    return batch, {"seg_offsets": part.row_offsets(),
+                   "seg_part": np.arange(part.nparts, dtype=np.int32),
+                   "n_parts": part.nparts}
+
+
+def exchanged_batch(ex: Exchanged):
+    """(batch, layout) of an Exchanged window: a non-owning device view over its buffers
+    plus {"seg_offsets", "seg_part", "n_parts"} derived from row_counts(): producer-major, then
+    partition-major per producer, so segment s holds partition s % parts. Nothing is
+    copied; `ex` must outlive the view."""
+    L = lib()
+    counts = ex.row_counts()
+    n_prod, n_parts = counts.shape
+    seg_offsets = np.zeros(n_prod * n_parts + 1, dtype=np.int64)
+    np.cumsum(counts.reshape(-1)[:n_prod * n_parts], out=seg_offsets[1:])
+    seg_part = (np.arange(n_prod * n_parts) % n_parts).astype(np.int32)
+    batch = _output_view(ex.part.batch, lambda i: L.dd_exchanged_col_data(ex.h, i),
+                         lambda i: L.dd_exchanged_col_validity(ex.h, i), int(ex.total_rows))
+    return batch, {"seg_offsets": seg_offsets, "seg_part": seg_part, "n_parts": int(n_parts)}

@@ -2468,6 +2468,293 @@ extern "C" int32_t dd_reducer_waveagg(const dd_reducer *r) { return r->waveagg; 
 
 extern "C" void dd_reducer_destroy(dd_reducer *r) { delete r; }
 
+/* ---------------- final aggregation above the shuffle (dd_finalizer) ------ */
+
+struct dd_finalizer {
+    int32_t n_keys = 0, n_aggs = 0, n_parts = 0;
+    int64_t n_groups = 0;
+    std::vector<int64_t> group_offsets; /* [n_parts + 1] */
+    uint64_t *keys = nullptr;           /* [n_groups][n_keys] */
+    uint32_t *keynull = nullptr;        /* [n_groups] */
+    uint64_t *aggs = nullptr;           /* [n_groups][n_aggs] */
+    uint64_t *hi = nullptr;
+    uint64_t *nn = nullptr;
+    float kernel_ms[3] = {0, 0, 0}; /* claim, scan, merge */
+    ~dd_finalizer() {
+        (void)hipFree(keys);
+        (void)hipFree(keynull);
+        (void)hipFree(aggs);
+        (void)hipFree(hi);
+        (void)hipFree(nn);
+    }
+};
+
+/* claim-table region of a partition with `rows` rows: max(64, next_pow2(2 * rows)) slots,
+ * returned as its log2 (finalagg.table_slots is the same arithmetic) */
+static uint32_t dd_final_region_log2(int64_t rows) {
+    uint32_t lg = 6;
+    static_assert((1 << 6) == DD_F_MIN_SLOTS, "smallest region");
+    while (((int64_t)1 << lg) < 2 * rows) lg++;
+    return lg;
+}
+
+/* frees every device pointer handed to it when it goes out of scope */
+struct dd_dev_scratch {
+    std::vector<void *> ptrs;
+    template <typename T> bool alloc(T **p, size_t bytes) {
+        void *v = nullptr;
+        if (hipMalloc(&v, bytes ? bytes : 1) != hipSuccess) return false;
+        ptrs.push_back(v);
+        *p = (T *)v;
+        return true;
+    }
+    ~dd_dev_scratch() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+};
+
+extern "C" dd_status dd_final_merge_run(const dd_batch_desc *batch, const int32_t *key_cols,
+                                        int32_t n_keys, const int32_t *state_cols,
+                                        const int32_t *agg_ops, const int32_t *nn_cols,
+                                        int32_t n_aggs, const int64_t *seg_offsets,
+                                        const int32_t *seg_part, int32_t n_segs,
+                                        int32_t n_parts, void *stream, dd_finalizer **out) {
+    if (!batch || !key_cols || !state_cols || !agg_ops || !nn_cols || !seg_offsets ||
+        !seg_part || !out)
+        return set_err(DD_ERR_INVALID, "final merge: null argument");
+    if (n_keys < 1 || n_keys > 4)
+        return set_err(DD_ERR_UNSUPPORTED, "final merge: 1..4 key columns");
+    if (n_aggs < 1)
+        return set_err(DD_ERR_UNSUPPORTED, "final merge: at least 1 aggregate");
+    if (n_aggs > DD_F_MAX_AGGS)
+        return set_err(DD_ERR_UNSUPPORTED, "final merge: at most 8 aggregates");
+    const int64_t n = batch->n_rows;
+    if (n < 0 || n >= ((int64_t)1 << 31))
+        return set_err(DD_ERR_INVALID, "final merge: n_rows must be below 2^31 (row ids are "
+                                       "32-bit table entries)");
+    if (batch->n_cols < 1 || batch->n_cols > DD_MAX_COLS)
+        return set_err(DD_ERR_INVALID, "final merge: column count out of range");
+    for (int k = 0; k < n_keys; k++) {
+        if (key_cols[k] < 0 || key_cols[k] >= batch->n_cols)
+            return set_err(DD_ERR_INVALID, "final merge: key column out of range");
+        switch (batch->cols[key_cols[k]].dtype) {
+        case DD_DT_DICT32:
+            return set_err(DD_ERR_UNSUPPORTED,
+                           "final merge: dict32 keys are not supported: rebased indices "
+                           "after a GC'd exchange must be merged by value");
+        case DD_DT_UTF8:
+            return set_err(DD_ERR_UNSUPPORTED,
+                           "final merge: utf8 / utf8view keys are not supported");
+        case DD_DT_DEC128:
+            return set_err(DD_ERR_UNSUPPORTED, "final merge: dec128 keys are not supported");
+        case DD_DT_U8: case DD_DT_BOOL: case DD_DT_I16: case DD_DT_I32: case DD_DT_I64:
+        case DD_DT_F32: case DD_DT_F64:
+            break;
+        default:
+            return set_err(DD_ERR_INVALID, "final merge: unknown key dtype");
+        }
+    }
+    dd_final_plan plan;
+    memset(&plan, 0, sizeof(plan));
+    plan.n_aggs = n_aggs;
+    for (int g = 0; g < n_aggs; g++) {
+        const int op = agg_ops[g];
+        if (op < 0 || op > DD_AGG_SUM_DEC128)
+            return set_err(DD_ERR_INVALID, "final merge: unknown aggregate op");
+        if (state_cols[g] < 0 || state_cols[g] >= batch->n_cols)
+            return set_err(DD_ERR_INVALID, "final merge: state column out of range");
+        const dd_col_desc &sc = batch->cols[state_cols[g]];
+        if (op == DD_AGG_SUM_DEC128) {
+            if (sc.dtype != DD_DT_DEC128)
+                return set_err(DD_ERR_UNSUPPORTED,
+                               "final merge: a sum_dec128 state must be a dec128 column");
+            if ((uintptr_t)sc.data % 16)
+                return set_err(DD_ERR_INVALID, "final merge: dec128 data must be 16-byte "
+                                               "aligned");
+        } else if (op == DD_AGG_SUM_F64 || op == DD_AGG_MIN_F64 || op == DD_AGG_MAX_F64) {
+            if (sc.dtype != DD_DT_F64)
+                return set_err(DD_ERR_UNSUPPORTED,
+                               "final merge: an f64 aggregate's state must be an f64 column");
+        } else if (sc.dtype != DD_DT_I64) {
+            return set_err(DD_ERR_UNSUPPORTED,
+                           "final merge: a count / i64 aggregate's state must be an i64 "
+                           "column");
+        }
+        plan.ops[g] = op;
+        plan.state_cols[g] = state_cols[g];
+        if (op == DD_AGG_COUNT) continue; /* nn is the merged count; nn_col is -1 */
+        if (nn_cols[g] < 0 || nn_cols[g] >= batch->n_cols)
+            return set_err(DD_ERR_INVALID, "final merge: nn column out of range");
+        if (batch->cols[nn_cols[g]].dtype != DD_DT_I64)
+            return set_err(DD_ERR_UNSUPPORTED, "final merge: an nn column must be i64");
+        plan.nn_cols[g] = nn_cols[g];
+    }
+    /* segment layout -> rows per partition -> table regions */
+    if (n_segs < 1 || n_parts < 1)
+        return set_err(DD_ERR_INVALID, "final merge: malformed segment layout: at least one "
+                                       "segment and one partition");
+    if (seg_offsets[0] != 0 || seg_offsets[n_segs] != n)
+        return set_err(DD_ERR_INVALID, "final merge: malformed segment layout: seg_offsets "
+                                       "must run from 0 to n_rows");
+    std::vector<int64_t> rows_p((size_t)n_parts, 0);
+    for (int s = 0; s < n_segs; s++) {
+        if (seg_offsets[s + 1] < seg_offsets[s])
+            return set_err(DD_ERR_INVALID, "final merge: malformed segment layout: "
+                                           "seg_offsets decrease");
+        if (seg_part[s] < 0 || seg_part[s] >= n_parts)
+            return set_err(DD_ERR_INVALID, "final merge: malformed segment layout: seg_part "
+                                           "outside [0, n_parts)");
+        rows_p[seg_part[s]] += seg_offsets[s + 1] - seg_offsets[s];
+    }
+    std::vector<uint32_t> base_h((size_t)n_parts), log2_h((size_t)n_parts);
+    uint64_t n_slots = 0;
+    for (int p = 0; p < n_parts; p++) {
+        log2_h[p] = dd_final_region_log2(rows_p[p]);
+        if (n_slots >= ((uint64_t)1 << 32))
+            break;
+        base_h[p] = (uint32_t)n_slots;
+        n_slots += (uint64_t)1 << log2_h[p];
+    }
+    if (n_slots >= ((uint64_t)1 << 32))
+        return set_err(DD_ERR_UNSUPPORTED, "final merge: claim table past 2^32 slots");
+
+    auto f = std::unique_ptr<dd_finalizer>(new dd_finalizer());
+    f->n_keys = n_keys;
+    f->n_aggs = n_aggs;
+    f->n_parts = n_parts;
+    f->group_offsets.assign((size_t)n_parts + 1, 0);
+    if (n == 0) { /* zero groups, no device work */
+        *out = f.release();
+        return DD_OK;
+    }
+    if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
+
+    dd_kargs ka;
+    memset(&ka, 0, sizeof(ka));
+    ka.n_rows = n;
+    ka.n_cols = batch->n_cols;
+    ka.n_keys = n_keys;
+    for (int k = 0; k < n_keys; k++) ka.key_idx[k] = key_cols[k];
+    for (int c = 0; c < batch->n_cols; c++) {
+        const dd_col_desc &cd = batch->cols[c];
+        dd_kcol &kc = ka.cols[c];
+        kc.dtype = cd.dtype;
+        kc.elem = fixed_elem_size(cd.dtype);
+        kc.data = cd.data;
+        kc.valid = cd.validity;
+        kc.offsets = cd.offsets;
+    }
+
+    hipStream_t s = (hipStream_t)stream;
+    dd_dev_scratch ws;
+    int64_t *d_seg_off = nullptr, *d_goff = nullptr;
+    int32_t *d_seg_part = nullptr;
+    uint32_t *d_base = nullptr, *d_log2 = nullptr, *table = nullptr, *slot_gid = nullptr,
+             *row_slot = nullptr, *block_sums = nullptr, *err = nullptr;
+    const size_t nb = (size_t)((n_slots + DD_F_SCAN_TILE - 1) / DD_F_SCAN_TILE);
+    if (!ws.alloc(&d_seg_off, ((size_t)n_segs + 1) * 8) ||
+        !ws.alloc(&d_seg_part, (size_t)n_segs * 4) || !ws.alloc(&d_base, (size_t)n_parts * 4) ||
+        !ws.alloc(&d_log2, (size_t)n_parts * 4) || !ws.alloc(&d_goff, ((size_t)n_parts + 1) * 8) ||
+        !ws.alloc(&table, (size_t)n_slots * 4) || !ws.alloc(&slot_gid, (size_t)n_slots * 4) ||
+        !ws.alloc(&row_slot, (size_t)n * 4) || !ws.alloc(&block_sums, (nb + 1) * 4) ||
+        !ws.alloc(&err, 4))
+        return set_err(DD_ERR_HIP, "final merge: workspace alloc");
+    hipEvent_t ev[5] = {};
+    struct ev_guard {
+        hipEvent_t *e;
+        ~ev_guard() {
+            for (int i = 0; i < 5; i++)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } evg{ev};
+    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemcpyAsync(d_seg_off, seg_offsets, ((size_t)n_segs + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_seg_part, seg_part, (size_t)n_segs * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_base, base_h.data(), (size_t)n_parts * 4, hipMemcpyHostToDevice,
+                           s));
+    HIP_TRY(hipMemcpyAsync(d_log2, log2_h.data(), (size_t)n_parts * 4, hipMemcpyHostToDevice,
+                           s));
+    HIP_TRY(hipMemsetAsync(err, 0, 4, s));
+    /* the host vectors above are pageable: the copies have left them before they die */
+    HIP_TRY(hipStreamSynchronize(s));
+
+    HIP_TRY(hipEventRecord(ev[0], s));
+    HIP_TRY(hipMemsetAsync(table, 0xff, (size_t)n_slots * 4, s)); /* DD_F_EMPTY */
+    HIP_TRY(dd_launch_final_claim(&ka, d_seg_off, d_seg_part, n_segs, d_base, d_log2, table,
+                                  row_slot, err, s));
+    HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(dd_launch_final_scan(table, n_slots, block_sums, slot_gid, d_base, n_parts, d_goff,
+                                 s));
+    HIP_TRY(hipEventRecord(ev[2], s));
+    HIP_TRY(hipMemcpyAsync(f->group_offsets.data(), d_goff, ((size_t)n_parts + 1) * 8,
+                           hipMemcpyDeviceToHost, s));
+    uint32_t err_h = 0;
+    HIP_TRY(hipMemcpyAsync(&err_h, err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err_h) return set_err(DD_ERR_HIP, "final merge: claim table overflow (internal)");
+    const int64_t ng = f->group_offsets[n_parts];
+    f->n_groups = ng;
+    /* state is sized by the groups found, not by the table */
+    HIP_TRY(hipMalloc((void **)&f->keys, (size_t)ng * n_keys * 8));
+    HIP_TRY(hipMalloc((void **)&f->keynull, (size_t)ng * 4));
+    HIP_TRY(hipMalloc((void **)&f->aggs, (size_t)ng * n_aggs * 8));
+    HIP_TRY(hipMalloc((void **)&f->hi, (size_t)ng * n_aggs * 8));
+    HIP_TRY(hipMalloc((void **)&f->nn, (size_t)ng * n_aggs * 8));
+    HIP_TRY(hipEventRecord(ev[3], s));
+    HIP_TRY(dd_launch_final_merge(&ka, &plan, table, row_slot, slot_gid, ng, f->keys,
+                                  f->keynull, f->aggs, f->hi, f->nn, s));
+    HIP_TRY(hipEventRecord(ev[4], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&f->kernel_ms[0], ev[0], ev[1]);
+    (void)hipEventElapsedTime(&f->kernel_ms[1], ev[1], ev[2]);
+    (void)hipEventElapsedTime(&f->kernel_ms[2], ev[3], ev[4]);
+    *out = f.release();
+    return DD_OK;
+}
+
+extern "C" int64_t dd_finalizer_n_groups(const dd_finalizer *f) { return f->n_groups; }
+
+extern "C" dd_status dd_finalizer_group_offsets(const dd_finalizer *f, int64_t *host_out) {
+    if (!f || !host_out) return set_err(DD_ERR_INVALID, "null argument");
+    memcpy(host_out, f->group_offsets.data(), f->group_offsets.size() * 8);
+    return DD_OK;
+}
+
+extern "C" dd_status dd_finalizer_fetch(const dd_finalizer *f, uint64_t *host_keys,
+                                        uint32_t *host_keynull, double *host_aggs) {
+    if (f->n_groups == 0) return DD_OK;
+    HIP_TRY(hipMemcpy(host_keys, f->keys, (size_t)f->n_groups * f->n_keys * 8,
+                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_keynull, f->keynull, (size_t)f->n_groups * 4,
+                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host_aggs, f->aggs, (size_t)f->n_groups * f->n_aggs * 8,
+                      hipMemcpyDeviceToHost));
+    return DD_OK;
+}
+
+extern "C" dd_status dd_finalizer_fetch_nn(const dd_finalizer *f, uint64_t *host_nn) {
+    if (f->n_groups == 0) return DD_OK;
+    HIP_TRY(hipMemcpy(host_nn, f->nn, (size_t)f->n_groups * f->n_aggs * 8,
+                      hipMemcpyDeviceToHost));
+    return DD_OK;
+}
+
+extern "C" dd_status dd_finalizer_fetch_hi(const dd_finalizer *f, uint64_t *host_hi) {
+    if (f->n_groups == 0) return DD_OK;
+    HIP_TRY(hipMemcpy(host_hi, f->hi, (size_t)f->n_groups * f->n_aggs * 8,
+                      hipMemcpyDeviceToHost));
+    return DD_OK;
+}
+
+extern "C" dd_status dd_finalizer_kernel_ms(const dd_finalizer *f, float *out3) {
+    if (!f || !out3) return set_err(DD_ERR_INVALID, "null argument");
+    memcpy(out3, f->kernel_ms, sizeof(f->kernel_ms));
+    return DD_OK;
+}
+
+extern "C" void dd_finalizer_destroy(dd_finalizer *f) { delete f; }
+
 /* ---------------- coalesce (dd_coalesce_run) ---------------- */
 
 /* task_group (network_coalesce.rs:376-400): contiguous ceil-split of producers */

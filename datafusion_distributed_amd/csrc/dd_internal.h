@@ -37,6 +37,16 @@
 #define DD_RW_MAX_BLOCKS 2048
 #define DD_RW_PEEL_MIN 8       /* wave aggregation: smallest lane group worth a reduce */
 
+/* final merge above the shuffle (dd_final.hip) */
+#define DD_F_MAX_AGGS 8
+#define DD_F_THREADS 256
+#define DD_F_BLOCK_ROWS 2048  /* claim: rows per block, so the staged segment offsets are
+                                 read once per 2048 rows */
+#define DD_F_LDS_SEGS 1024    /* claim: segment offsets staged in LDS up to this many */
+#define DD_F_MIN_SLOTS 64     /* smallest claim-table region of a partition */
+#define DD_F_SCAN_TILE 1024   /* scan: table entries per block, 4 per thread */
+#define DD_F_EMPTY 0xffffffffu
+
 /* dtype codes mirror dd_dtype in include/dd_shuffle.h */
 enum {
     DD_KDT_U8 = 1,
@@ -102,6 +112,14 @@ struct dd_kargs {
     int32_t key_idx[DD_KMAX_KEYS];
     int32_t var_idx[DD_KMAX_VAR];
     dd_kcol cols[DD_KMAX_COLS];
+};
+
+/* the plan of a final merge, passed by value so every field is wave-uniform */
+struct dd_final_plan {
+    int32_t n_aggs;
+    int32_t ops[DD_F_MAX_AGGS];        /* DD_AGG_* read as merge ops */
+    int32_t state_cols[DD_F_MAX_AGGS]; /* partial state column per aggregate */
+    int32_t nn_cols[DD_F_MAX_AGGS];    /* i64 non-null-count column; unused for COUNT */
 };
 
 /* dictionary GC (dd_dictgc.hip): one workgroup per row tile; a tile never straddles a
@@ -273,6 +291,25 @@ hipError_t dd_launch_partial_reduce_wide(const dd_kargs *a, int waveagg, int64_t
                                          uint64_t *out_keys, uint32_t *out_keynull,
                                          uint64_t *out_aggs, uint64_t *out_hi,
                                          uint64_t *out_nn, uint64_t *out_n, hipStream_t s);
+/* final merge (dd_final.hip). table / slot_gid: n_slots u32 entries, n_slots a multiple
+ * of 4; part_base / part_log2: region base and log2(region slots) per partition */
+hipError_t dd_launch_final_claim(const dd_kargs *a, const int64_t *seg_offsets,
+                                 const int32_t *seg_part, int32_t n_segs,
+                                 const uint32_t *part_base, const uint32_t *part_log2,
+                                 uint32_t *table, uint32_t *row_slot, uint32_t *err,
+                                 hipStream_t s);
+/* block_sums: n_slots / DD_F_SCAN_TILE (rounded up) + 1 entries; group_offsets: device
+ * int64[n_parts + 1] */
+hipError_t dd_launch_final_scan(const uint32_t *table, uint64_t n_slots,
+                                uint32_t *block_sums, uint32_t *slot_gid,
+                                const uint32_t *part_base, int32_t n_parts,
+                                int64_t *group_offsets, hipStream_t s);
+hipError_t dd_launch_final_merge(const dd_kargs *a, const dd_final_plan *plan,
+                                 const uint32_t *table, const uint32_t *row_slot,
+                                 const uint32_t *slot_gid, int64_t n_groups,
+                                 uint64_t *out_keys, uint32_t *out_keynull,
+                                 uint64_t *out_aggs, uint64_t *out_hi, uint64_t *out_nn,
+                                 hipStream_t s);
 }
 
 #endif

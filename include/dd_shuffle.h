@@ -613,6 +613,66 @@ int32_t dd_reducer_kernel(const dd_reducer *r);
 int32_t dd_reducer_waveagg(const dd_reducer *r);
 void dd_reducer_destroy(dd_reducer *r);
 
+/* ---------------- final aggregation (above the shuffle) ----------------
+ * The other half of the two-phase aggregate: the AggregateExec mode=FinalPartitioned that
+ * sits on RepartitionExec Hash([l_returnflag, l_linestatus], 6) in the q1 plan of
+ * tests/tpch_plans_test.rs. Input: a device batch of PARTIAL STATES (what
+ * dd_partial_reduce_run produced and the shuffle carried) plus a segment layout; output:
+ * exactly one row per (partition, group), partition-major. DESIGN.md §18 is normative.
+ *
+ * Segment layout (host arrays): seg_offsets[n_segs + 1] non-decreasing row offsets from 0
+ * to n_rows; seg_part[n_segs] the partition of each segment, in [0, n_parts). The rows of
+ * all segments with one partition id form that partition. A dd_partitioner output is
+ * n_segs = P, seg_part = identity; a dd_exchanged window (producer-major, then
+ * partition-major per producer) is n_segs = producers * parts, seg_part[s] = s % parts;
+ * n_segs = n_parts = 1 is a plain global group-by.
+ *
+ * Groups are formed WITHIN a partition (one key in two partitions gives two groups) by the
+ * identity dd_reducer_fetch reports: canonical u64 key bits plus the key-null mask; a NULL
+ * component has bits 0 and its mask bit set. Keys: 1..4 of u8, bool, i16, i32, i64, f32, f64.
+ *
+ * Aggregates: 1..8 of (state_col, op, nn_col), DD_AGG_* read as merge ops. COUNT adds an i64
+ * column of partial counts (nn_col ignored, pass -1; nn is the merged count); SUM_I64 wraps
+ * modulo 2^64; SUM_F64 adds in an unspecified order; MIN / MAX as in the partial aggregate
+ * (signed; totalOrder on the bit pattern, payloads preserved); SUM_DEC128 adds (lo, hi)
+ * modulo 2^128. nn_col is an i64 column of non-null input counts: a partial with nn == 0 is
+ * skipped, nn is summed per group, and a total of 0 means SQL NULL (value unspecified).
+ * Validity buffers of state and nn columns are ignored, as are columns the plan does not
+ * name. The order of groups inside a partition is unspecified.
+ *
+ * DD_ERR_UNSUPPORTED, with a message that names the cause: a dict32 (rebased indices after
+ * a GC'd exchange must be merged by value), utf8 or dec128 key; a state or nn column of the
+ * wrong dtype for its op; more than 8 aggregates or 4 keys. DD_ERR_INVALID: a malformed
+ * segment layout, a column index out of range, n_rows >= 2^31. n_rows == 0 succeeds with
+ * zero groups. Synchronous on `stream`. */
+
+typedef struct dd_finalizer dd_finalizer;
+
+/* seam: the final aggregate above RepartitionExec in the q1 plan (tests/tpch_plans_test.rs) */
+dd_status dd_final_merge_run(const dd_batch_desc *batch, const int32_t *key_cols,
+                             int32_t n_keys, const int32_t *state_cols,
+                             const int32_t *agg_ops, const int32_t *nn_cols, int32_t n_aggs,
+                             const int64_t *seg_offsets, const int32_t *seg_part,
+                             int32_t n_segs, int32_t n_parts, void *stream,
+                             dd_finalizer **out);
+/* same seam: output rows of the final aggregate, one per (partition, group) */
+int64_t dd_finalizer_n_groups(const dd_finalizer *f);
+/* same seam: host_out[n_parts + 1], partition p's groups are rows [out[p], out[p + 1]) --
+ * the output partitioning the FinalPartitioned aggregate keeps from RepartitionExec */
+dd_status dd_finalizer_group_offsets(const dd_finalizer *f, int64_t *host_out);
+/* same seam: the merged rows in the shapes of dd_reducer_fetch: host_keys[n][n_keys],
+ * host_keynull[n], host_aggs[n][n_aggs] (integers bit-cast; min / max as value bits) */
+dd_status dd_finalizer_fetch(const dd_finalizer *f, uint64_t *host_keys,
+                             uint32_t *host_keynull, double *host_aggs);
+/* same seam: host_nn[n][n_aggs] summed non-null counts; 0 = the aggregate is SQL NULL */
+dd_status dd_finalizer_fetch_nn(const dd_finalizer *f, uint64_t *host_nn);
+/* same seam: host_hi[n][n_aggs] high 64 bits of each SUM_DEC128, 0 for every other op */
+dd_status dd_finalizer_fetch_hi(const dd_finalizer *f, uint64_t *host_hi);
+/* same seam: hipEvent times of the run in ms: out3 = [claim, scan, merge] */
+dd_status dd_finalizer_kernel_ms(const dd_finalizer *f, float *out3);
+/* same seam: frees the merged rows */
+void dd_finalizer_destroy(dd_finalizer *f);
+
 /* ---------------- device helpers (harness convenience; not part of the seam) ------- */
 dd_status dd_dev_alloc(int64_t bytes, void **out);
 dd_status dd_dev_free(void *p);
