@@ -124,6 +124,16 @@ def lib():
         L.dd_finalizer_n_groups.restype = ctypes.c_int64
         L.dd_finalizer_destroy.restype = None
         L.dd_finalizer_destroy.argtypes = [ctypes.c_void_p]
+        L.dd_joiner_n_rows.restype = ctypes.c_int64
+        L.dd_joiner_n_rows.argtypes = [ctypes.c_void_p]
+        for fn in (L.dd_joiner_build_idx, L.dd_joiner_probe_idx):
+            fn.restype = ctypes.c_void_p
+            fn.argtypes = [ctypes.c_void_p]
+        for fn in (L.dd_joiner_col_data, L.dd_joiner_col_validity):
+            fn.restype = ctypes.c_void_p
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+        L.dd_joiner_destroy.restype = None
+        L.dd_joiner_destroy.argtypes = [ctypes.c_void_p]
         L.dd_dict_gc_n_windows.restype = ctypes.c_uint32
         L.dd_dict_gc_indices.restype = ctypes.c_void_p
         L.dd_dict_gc_dict_offsets.restype = ctypes.c_void_p
@@ -1127,3 +1137,140 @@ def exchanged_batch(ex: Exchanged):
     batch = _output_view(ex.part.batch, lambda i: L.dd_exchanged_col_data(ex.h, i),
                          lambda i: L.dd_exchanged_col_validity(ex.h, i), int(ex.total_rows))
     return batch, {"seg_offsets": seg_offsets, "seg_part": seg_part, "n_parts": int(n_parts)}
+
+
+JOIN_TYPES = {"inner": 0, "left_semi": 1, "left_anti": 2, "right_semi": 3, "right_anti": 4,
+              "left": 5, "right": 6, "full": 7}
+
+
+class Joined:
+    """Output of hash_join (dd_joiner_*): pair indices and the projected columns, all on
+    the device, plus the emitting side's segment layout with new offsets."""
+
+    def __init__(self, h, join_type, out_cols, seg_part, n_parts):
+        self.h = h
+        self.join_type = join_type
+        self._out_cols = out_cols  # (dtype, source has validity) per output column
+        self._seg_part = seg_part
+        self._n_parts = n_parts
+        self.n_rows = int(lib().dd_joiner_n_rows(h))
+
+    def seg_offsets(self):
+        """Host i64[S + 1] over the output rows; S and seg_part are the emitting side's."""
+        out = np.zeros(len(self._seg_part) + 1, dtype=np.int64)
+        _check(lib().dd_joiner_seg_offsets(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def layout(self):
+        return {"seg_offsets": self.seg_offsets(), "seg_part": self._seg_part.copy(),
+                "n_parts": self._n_parts}
+
+    def pairs_ptr(self):
+        """(build_idx, probe_idx) device pointers to u32[n_rows]; None for the side a semi /
+        anti join does not emit, and for both when the emitting side had no rows."""
+        return lib().dd_joiner_build_idx(self.h), lib().dd_joiner_probe_idx(self.h)
+
+    def pairs(self):
+        """(build_idx, probe_idx) as host u32[n_rows] copies (tests); None for the side a
+        semi / anti join does not emit."""
+        emitted = (not self.join_type.startswith("right_"),
+                   not self.join_type.startswith("left_"))
+        return tuple(None if not e else
+                     _d2h(p, self.n_rows * 4, np.uint32) if self.n_rows else
+                     np.zeros(0, dtype=np.uint32)
+                     for e, p in zip(emitted, self.pairs_ptr()))
+
+    def batch(self):
+        """(view, layout): a non-owning DeviceBatch over the output columns (build_proj
+        first) plus {"seg_offsets", "seg_part", "n_parts"}, ready for final_merge,
+        partial_reduce or Partitioner. Nothing is copied; this Joined must outlive it."""
+        if not self._out_cols:
+            raise ValueError("hash_join: no projected columns, so there is no batch (pairs only)")
+        L = lib()
+        view = [{"dtype": dt, "data_ptr": L.dd_joiner_col_data(self.h, i),
+                 "valid_ptr": L.dd_joiner_col_validity(self.h, i)}
+                for i, (dt, _) in enumerate(self._out_cols)]
+        return DeviceBatch.from_device(view, self.n_rows), self.layout()
+
+    def col(self, i):
+        """Host copy of output column i in Partitioner.col_out's shape (tests)."""
+        dt, has_valid = self._out_cols[i]
+        n = self.n_rows
+        res = {"dtype": dt, "data": fixed_out(dt, np.zeros(0, dtype=FIXED_NP[dt]))}
+        if n:
+            res["data"] = fixed_out(dt, _d2h(lib().dd_joiner_col_data(self.h, i),
+                                             n * ELEM_SIZE[dt], FIXED_NP[dt]))
+        if has_valid:
+            res["valid"] = (_d2h(lib().dd_joiner_col_validity(self.h, i), n, np.uint8) if n
+                            else np.zeros(0, dtype=np.uint8))
+        return res
+
+    def kernel_ms(self):
+        """[build, count, scan, emit, gather] hipEvent times in ms."""
+        out = (ctypes.c_float * 5)()
+        _check(lib().dd_joiner_kernel_ms(self.h, out))
+        return list(out)
+
+    def destroy(self):
+        if self.h:
+            lib().dd_joiner_destroy(self.h)
+            self.h = None
+
+
+def _join_layout(layout, n_rows):
+    if layout is None:
+        layout = {"seg_offsets": [0, n_rows], "seg_part": [0], "n_parts": 1}
+    off = np.ascontiguousarray(layout["seg_offsets"], dtype=np.int64)
+    part = np.ascontiguousarray(layout["seg_part"], dtype=np.int32)
+    if len(off) != len(part) + 1:
+        raise ValueError("hash_join: seg_offsets must have one entry more than seg_part")
+    return off, part, int(layout["n_parts"])
+
+
+def hash_join(build: DeviceBatch, build_keys, probe: DeviceBatch, probe_keys,
+              join_type="inner", build_layout=None, probe_layout=None, build_proj=None,
+              probe_proj=None):
+    """GPU partitioned hash join above two co-partitioned shuffles (dd_hash_join_run;
+    DESIGN.md §19): HashJoinExec mode=Partitioned with `build` as its left side.
+
+    build_keys / probe_keys: 1..4 key columns per side, pairwise of one dtype out of u8,
+    bool, i16, i32, i64; a row with a NULL in any key component matches nothing.
+    join_type: "inner", "left_semi", "left_anti" (build rows), "right_semi", "right_anti"
+    (probe rows).
+    build_layout / probe_layout: {"seg_offsets", "seg_part", "n_parts"} as exchanged_batch
+    and partitioned_batch return them; partition p joins partition p only, and n_parts must
+    be equal. Default: one segment, one partition (a plain hash join).
+    build_proj / probe_proj: output column indices, build columns first; default: all
+    columns of the side(s) the join type emits. Fixed-width dtypes only.
+    Returns a Joined. Output rows follow the emitting side's row order (probe for inner and
+    right_*, build for left_*) and keep its segments."""
+    if join_type not in JOIN_TYPES:
+        raise ValueError(f"hash_join: unknown join type {join_type!r}")
+    if len(build_keys) != len(probe_keys):
+        raise ValueError("hash_join: the two sides need the same number of key columns")
+    nk = len(build_keys)
+    emits_build = not join_type.startswith("right_")
+    emits_probe = not join_type.startswith("left_")
+    if build_proj is None:
+        build_proj = list(range(build.desc.n_cols)) if emits_build else []
+    if probe_proj is None:
+        probe_proj = list(range(probe.desc.n_cols)) if emits_probe else []
+    boff, bpart, bparts = _join_layout(build_layout, build.n_rows)
+    poff, ppart, pparts = _join_layout(probe_layout, probe.n_rows)
+    bk = (ctypes.c_int32 * max(nk, 1))(*build_keys)
+    pk = (ctypes.c_int32 * max(nk, 1))(*probe_keys)
+    bp = (ctypes.c_int32 * max(len(build_proj), 1))(*build_proj)
+    pp = (ctypes.c_int32 * max(len(probe_proj), 1))(*probe_proj)
+    h = ctypes.c_void_p()
+    _check(lib().dd_hash_join_run(
+        ctypes.byref(build.desc), bk, ctypes.byref(probe.desc), pk, ctypes.c_int32(nk),
+        ctypes.c_int32(JOIN_TYPES[join_type]),
+        boff.ctypes.data_as(ctypes.c_void_p), bpart.ctypes.data_as(ctypes.c_void_p),
+        ctypes.c_int32(len(bpart)), ctypes.c_int32(bparts),
+        poff.ctypes.data_as(ctypes.c_void_p), ppart.ctypes.data_as(ctypes.c_void_p),
+        ctypes.c_int32(len(ppart)), ctypes.c_int32(pparts),
+        bp, ctypes.c_int32(len(build_proj)), pp, ctypes.c_int32(len(probe_proj)),
+        None, ctypes.byref(h)))
+    out_cols = [(b.cols[i]["dtype"], bool(b.desc.cols[i].validity))
+                for b, proj in ((build, build_proj), (probe, probe_proj)) for i in proj]
+    return Joined(h, join_type, out_cols, ppart if emits_probe else bpart, bparts)

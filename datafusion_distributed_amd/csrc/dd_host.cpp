@@ -2755,6 +2755,346 @@ extern "C" dd_status dd_finalizer_kernel_ms(const dd_finalizer *f, float *out3) 
 
 extern "C" void dd_finalizer_destroy(dd_finalizer *f) { delete f; }
 
+/* ---------------- hash join above two shuffles (dd_joiner) ---------------- */
+
+struct dd_joiner {
+    int64_t n_rows = 0;
+    std::vector<int64_t> seg_offsets; /* [emitting side's n_segs + 1] */
+    uint32_t *build_idx = nullptr, *probe_idx = nullptr;
+    std::vector<void *> col_data;        /* per output column; null only at zero rows */
+    std::vector<uint8_t *> col_validity; /* null when the source has none */
+    float kernel_ms[5] = {0, 0, 0, 0, 0}; /* build, count, scan, emit, gather */
+    ~dd_joiner() {
+        (void)hipFree(build_idx);
+        (void)hipFree(probe_idx);
+        for (void *p : col_data) (void)hipFree(p);
+        for (uint8_t *p : col_validity) (void)hipFree(p);
+    }
+};
+
+/* §18.1's layout checks for one side; rows_p: rows per partition */
+static dd_status dd_join_check_layout(const char *side, int64_t n, const int64_t *seg_offsets,
+                                      const int32_t *seg_part, int32_t n_segs, int32_t n_parts,
+                                      std::vector<int64_t> *rows_p) {
+    const std::string who = std::string("hash join: malformed ") + side + " segment layout: ";
+    if (n_segs < 1 || n_parts < 1)
+        return set_err(DD_ERR_INVALID, who + "at least one segment and one partition");
+    if (seg_offsets[0] != 0 || seg_offsets[n_segs] != n)
+        return set_err(DD_ERR_INVALID, who + "seg_offsets must run from 0 to n_rows");
+    rows_p->assign((size_t)n_parts, 0);
+    for (int s = 0; s < n_segs; s++) {
+        if (seg_offsets[s + 1] < seg_offsets[s])
+            return set_err(DD_ERR_INVALID, who + "seg_offsets decrease");
+        if (seg_part[s] < 0 || seg_part[s] >= n_parts)
+            return set_err(DD_ERR_INVALID, who + "seg_part outside [0, n_parts)");
+        (*rows_p)[seg_part[s]] += seg_offsets[s + 1] - seg_offsets[s];
+    }
+    return DD_OK;
+}
+
+/* key and projection checks of one side */
+static dd_status dd_join_check_side(const char *side, const dd_batch_desc *b,
+                                    const int32_t *keys, int32_t n_keys, const int32_t *proj,
+                                    int32_t n_proj) {
+    const std::string who = std::string("hash join: ") + side + " ";
+    if (b->n_rows < 0 || b->n_rows >= ((int64_t)1 << 31))
+        return set_err(DD_ERR_INVALID, who + "n_rows must be below 2^31 (row ids are 32-bit "
+                                             "table entries)");
+    if (b->n_cols < 1 || b->n_cols > DD_MAX_COLS)
+        return set_err(DD_ERR_INVALID, who + "column count out of range");
+    for (int k = 0; k < n_keys; k++) {
+        if (keys[k] < 0 || keys[k] >= b->n_cols)
+            return set_err(DD_ERR_INVALID, who + "key column index out of range");
+        switch (b->cols[keys[k]].dtype) {
+        case DD_DT_F32: case DD_DT_F64:
+            return set_err(DD_ERR_UNSUPPORTED,
+                           who + "f32 / f64 keys are not supported: Arrow compares float join "
+                                 "keys by total order, the key bits here canonicalise -0.0 "
+                                 "and NaN");
+        case DD_DT_DICT32:
+            return set_err(DD_ERR_UNSUPPORTED, who + "dict32 keys are not supported");
+        case DD_DT_UTF8:
+            return set_err(DD_ERR_UNSUPPORTED, who + "utf8 / utf8view keys are not supported");
+        case DD_DT_DEC128:
+            return set_err(DD_ERR_UNSUPPORTED, who + "dec128 keys are not supported");
+        case DD_DT_U8: case DD_DT_BOOL: case DD_DT_I16: case DD_DT_I32: case DD_DT_I64:
+            break;
+        default:
+            return set_err(DD_ERR_INVALID, who + "unknown key dtype");
+        }
+    }
+    if (n_proj < 0 || n_proj > DD_MAX_COLS || (n_proj > 0 && !proj))
+        return set_err(DD_ERR_INVALID, who + "projection list out of range");
+    for (int i = 0; i < n_proj; i++) {
+        if (proj[i] < 0 || proj[i] >= b->n_cols)
+            return set_err(DD_ERR_INVALID, who + "projected column index out of range");
+        const dd_col_desc &cd = b->cols[proj[i]];
+        if (cd.dtype == DD_DT_UTF8)
+            return set_err(DD_ERR_UNSUPPORTED,
+                           who + "projection: a var-width (utf8 / utf8view) column is not "
+                                 "supported");
+        if (cd.dtype == DD_DT_DICT32)
+            return set_err(DD_ERR_UNSUPPORTED,
+                           who + "projection: a dict32 column is not supported");
+        if (fixed_elem_size(cd.dtype) == 0)
+            return set_err(DD_ERR_INVALID, who + "projection: unknown dtype");
+        if (cd.dtype == DD_DT_DEC128 && (uintptr_t)cd.data % 16)
+            return set_err(DD_ERR_INVALID, who + "dec128 column data must be 16-byte aligned");
+    }
+    return DD_OK;
+}
+
+static void dd_join_kargs(const dd_batch_desc *b, const int32_t *keys, int32_t n_keys,
+                          dd_kargs *ka) {
+    memset(ka, 0, sizeof(*ka));
+    ka->n_rows = b->n_rows;
+    ka->n_cols = b->n_cols;
+    ka->n_keys = n_keys;
+    for (int k = 0; k < n_keys; k++) ka->key_idx[k] = keys[k];
+    for (int c = 0; c < b->n_cols; c++) {
+        const dd_col_desc &cd = b->cols[c];
+        dd_kcol &kc = ka->cols[c];
+        kc.dtype = cd.dtype;
+        kc.elem = fixed_elem_size(cd.dtype);
+        kc.data = cd.data;
+        kc.valid = cd.validity;
+        kc.offsets = cd.offsets;
+    }
+}
+
+extern "C" dd_status dd_hash_join_run(
+    const dd_batch_desc *build, const int32_t *build_keys, const dd_batch_desc *probe,
+    const int32_t *probe_keys, int32_t n_keys, int32_t join_type,
+    const int64_t *build_seg_offsets, const int32_t *build_seg_part, int32_t build_n_segs,
+    int32_t build_n_parts, const int64_t *probe_seg_offsets, const int32_t *probe_seg_part,
+    int32_t probe_n_segs, int32_t probe_n_parts, const int32_t *build_proj,
+    int32_t n_build_proj, const int32_t *probe_proj, int32_t n_probe_proj, void *stream,
+    dd_joiner **out) {
+    if (!build || !build_keys || !probe || !probe_keys || !build_seg_offsets ||
+        !build_seg_part || !probe_seg_offsets || !probe_seg_part || !out)
+        return set_err(DD_ERR_INVALID, "hash join: null argument");
+    if (join_type == DD_JOIN_LEFT || join_type == DD_JOIN_RIGHT || join_type == DD_JOIN_FULL)
+        return set_err(DD_ERR_UNSUPPORTED, "hash join: outer joins (left, right, full) are not "
+                                           "supported");
+    if (join_type < DD_JOIN_INNER || join_type > DD_JOIN_FULL)
+        return set_err(DD_ERR_INVALID, "hash join: unknown join type");
+    if (n_keys > 4) return set_err(DD_ERR_UNSUPPORTED, "hash join: more than 4 key columns");
+    if (n_keys < 1) return set_err(DD_ERR_INVALID, "hash join: at least 1 key column");
+    const bool left = join_type == DD_JOIN_LEFT_SEMI || join_type == DD_JOIN_LEFT_ANTI;
+    const bool right = join_type == DD_JOIN_RIGHT_SEMI || join_type == DD_JOIN_RIGHT_ANTI;
+    const bool anti = join_type == DD_JOIN_LEFT_ANTI || join_type == DD_JOIN_RIGHT_ANTI;
+    if (left && n_probe_proj != 0)
+        return set_err(DD_ERR_INVALID, "hash join: a left_semi / left_anti join emits build "
+                                       "rows: a probe-side projection list is not allowed");
+    if (right && n_build_proj != 0)
+        return set_err(DD_ERR_INVALID, "hash join: a right_semi / right_anti join emits probe "
+                                       "rows: a build-side projection list is not allowed");
+    dd_status st = dd_join_check_side("build side:", build, build_keys, n_keys, build_proj,
+                                      n_build_proj);
+    if (st != DD_OK) return st;
+    st = dd_join_check_side("probe side:", probe, probe_keys, n_keys, probe_proj, n_probe_proj);
+    if (st != DD_OK) return st;
+    for (int k = 0; k < n_keys; k++)
+        if (build->cols[build_keys[k]].dtype != probe->cols[probe_keys[k]].dtype)
+            return set_err(DD_ERR_INVALID, "hash join: key dtypes differ pairwise (key " +
+                                               std::to_string(k) + ")");
+    if (n_build_proj + n_probe_proj > DD_MAX_COLS)
+        return set_err(DD_ERR_INVALID, "hash join: more output columns than a batch holds");
+    std::vector<int64_t> rows_b, rows_p;
+    st = dd_join_check_layout("build", build->n_rows, build_seg_offsets, build_seg_part,
+                              build_n_segs, build_n_parts, &rows_b);
+    if (st != DD_OK) return st;
+    st = dd_join_check_layout("probe", probe->n_rows, probe_seg_offsets, probe_seg_part,
+                              probe_n_segs, probe_n_parts, &rows_p);
+    if (st != DD_OK) return st;
+    if (build_n_parts != probe_n_parts)
+        return set_err(DD_ERR_INVALID, "hash join: unequal n_parts: the two sides must be "
+                                       "co-partitioned");
+    const int32_t n_parts = build_n_parts;
+    /* table regions from the BUILD side's rows per partition (the final merge's sizing) */
+    std::vector<uint32_t> base_h((size_t)n_parts), log2_h((size_t)n_parts);
+    uint64_t n_slots = 0;
+    for (int p = 0; p < n_parts && n_slots < ((uint64_t)1 << 32); p++) {
+        log2_h[p] = dd_final_region_log2(rows_b[p]);
+        base_h[p] = (uint32_t)n_slots;
+        n_slots += (uint64_t)1 << log2_h[p];
+    }
+    if (n_slots >= ((uint64_t)1 << 32))
+        return set_err(DD_ERR_UNSUPPORTED, "hash join: build table past 2^32 slots");
+
+    const int64_t nb_rows = build->n_rows, np_rows = probe->n_rows;
+    /* the emitting side: its rows are scanned, its segments are kept */
+    const int64_t n_emit = left ? nb_rows : np_rows;
+    const int64_t *e_seg_offsets = left ? build_seg_offsets : probe_seg_offsets;
+    const int32_t e_n_segs = left ? build_n_segs : probe_n_segs;
+    const int n_out_cols = n_build_proj + n_probe_proj;
+
+    auto j = std::unique_ptr<dd_joiner>(new dd_joiner());
+    j->seg_offsets.assign((size_t)e_n_segs + 1, 0);
+    j->col_data.assign((size_t)n_out_cols, nullptr);
+    j->col_validity.assign((size_t)n_out_cols, nullptr);
+    if (n_emit == 0) { /* zero rows, no device work */
+        *out = j.release();
+        return DD_OK;
+    }
+    if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
+
+    dd_kargs kb, kp;
+    dd_join_kargs(build, build_keys, n_keys, &kb);
+    dd_join_kargs(probe, probe_keys, n_keys, &kp);
+
+    hipStream_t s = (hipStream_t)stream;
+    dd_dev_scratch ws;
+    int64_t *d_bseg_off = nullptr, *d_pseg_off = nullptr, *d_seg_out = nullptr;
+    int32_t *d_bseg_part = nullptr, *d_pseg_part = nullptr;
+    uint32_t *d_base = nullptr, *d_log2 = nullptr, *table = nullptr, *next = nullptr,
+             *cnt = nullptr, *err = nullptr;
+    uint64_t *sums = nullptr;
+    uint8_t *matched = nullptr;
+    const size_t n_pad = ((size_t)n_emit + 3) & ~(size_t)3;
+    const size_t nb = (n_pad + DD_J_SCAN_TILE - 1) / DD_J_SCAN_TILE;
+    if (!ws.alloc(&d_bseg_off, ((size_t)build_n_segs + 1) * 8) ||
+        !ws.alloc(&d_bseg_part, (size_t)build_n_segs * 4) ||
+        !ws.alloc(&d_pseg_off, ((size_t)probe_n_segs + 1) * 8) ||
+        !ws.alloc(&d_pseg_part, (size_t)probe_n_segs * 4) ||
+        !ws.alloc(&d_seg_out, ((size_t)e_n_segs + 2) * 8) ||
+        !ws.alloc(&d_base, (size_t)n_parts * 4) || !ws.alloc(&d_log2, (size_t)n_parts * 4) ||
+        !ws.alloc(&table, (size_t)n_slots * 4) || !ws.alloc(&next, (size_t)nb_rows * 4) ||
+        !ws.alloc(&cnt, n_pad * 4) || !ws.alloc(&sums, (nb + 1) * 8) || !ws.alloc(&err, 4) ||
+        (left && !ws.alloc(&matched, (size_t)nb_rows)))
+        return set_err(DD_ERR_HIP, "hash join: workspace alloc");
+    hipEvent_t ev[7] = {};
+    struct ev_guard {
+        hipEvent_t *e;
+        ~ev_guard() {
+            for (int i = 0; i < 7; i++)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } evg{ev};
+    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemcpyAsync(d_bseg_off, build_seg_offsets, ((size_t)build_n_segs + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_bseg_part, build_seg_part, (size_t)build_n_segs * 4,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_pseg_off, probe_seg_offsets, ((size_t)probe_n_segs + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_pseg_part, probe_seg_part, (size_t)probe_n_segs * 4,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_base, base_h.data(), (size_t)n_parts * 4, hipMemcpyHostToDevice,
+                           s));
+    HIP_TRY(hipMemcpyAsync(d_log2, log2_h.data(), (size_t)n_parts * 4, hipMemcpyHostToDevice,
+                           s));
+    HIP_TRY(hipMemsetAsync(err, 0, 4, s));
+    /* pageable host sources: the copies have left them before anything else happens */
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t *d_eseg_off = left ? d_bseg_off : d_pseg_off;
+
+    HIP_TRY(hipEventRecord(ev[0], s));
+    HIP_TRY(hipMemsetAsync(table, 0xff, (size_t)n_slots * 4, s)); /* DD_F_EMPTY */
+    if (nb_rows) HIP_TRY(hipMemsetAsync(next, 0xff, (size_t)nb_rows * 4, s));
+    HIP_TRY(dd_launch_join_build(&kb, d_bseg_off, d_bseg_part, build_n_segs, d_base, d_log2,
+                                 table, next, err, s));
+    HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(hipMemsetAsync(cnt, 0, n_pad * 4, s));
+    if (left) HIP_TRY(hipMemsetAsync(matched, 0, (size_t)nb_rows, s));
+    HIP_TRY(dd_launch_join_count(&kb, &kp, d_pseg_off, d_pseg_part, probe_n_segs, d_base,
+                                 d_log2, table, next, join_type, cnt, matched, s));
+    if (left) HIP_TRY(dd_launch_join_left_cnt(matched, nb_rows, anti, cnt, s));
+    HIP_TRY(hipEventRecord(ev[2], s));
+    HIP_TRY(dd_launch_join_scan(cnt, n_emit, sums, d_eseg_off, e_n_segs, d_seg_out, s));
+    HIP_TRY(hipEventRecord(ev[3], s));
+    /* the one mid-run sync: the output is sized by the result */
+    std::vector<int64_t> seg_out_h((size_t)e_n_segs + 2);
+    uint32_t err_h = 0;
+    HIP_TRY(hipMemcpyAsync(seg_out_h.data(), d_seg_out, ((size_t)e_n_segs + 2) * 8,
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&err_h, err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err_h) return set_err(DD_ERR_HIP, "hash join: build table overflow (internal)");
+    const uint64_t total = (uint64_t)seg_out_h[(size_t)e_n_segs + 1];
+    if (total >= ((uint64_t)1 << 31))
+        return set_err(DD_ERR_UNSUPPORTED, "hash join: output of " + std::to_string(total) +
+                                               " rows is 2^31 or more: chunk the probe side");
+    const int64_t n_out = (int64_t)total;
+    j->n_rows = n_out;
+    memcpy(j->seg_offsets.data(), seg_out_h.data(), ((size_t)e_n_segs + 1) * 8);
+
+    const size_t idx_bytes = n_out ? (size_t)n_out * 4 : 1;
+    if (!right) HIP_TRY(hipMalloc((void **)&j->build_idx, idx_bytes));
+    if (!left) HIP_TRY(hipMalloc((void **)&j->probe_idx, idx_bytes));
+    dd_join_gather gb, gp;
+    memset(&gb, 0, sizeof(gb));
+    memset(&gp, 0, sizeof(gp));
+    for (int i = 0; i < n_out_cols; i++) {
+        const bool from_build = i < n_build_proj;
+        const dd_col_desc &cd = from_build ? build->cols[build_proj[i]]
+                                           : probe->cols[probe_proj[i - n_build_proj]];
+        dd_join_gather &g = from_build ? gb : gp;
+        const int c = g.n_cols++;
+        g.elem[c] = fixed_elem_size(cd.dtype);
+        g.src[c] = cd.data;
+        g.src_valid[c] = (const uint8_t *)cd.validity;
+        HIP_TRY(hipMalloc(&j->col_data[i], n_out ? (size_t)n_out * g.elem[c] : 1));
+        g.dst[c] = j->col_data[i];
+        if (cd.validity) {
+            HIP_TRY(hipMalloc((void **)&j->col_validity[i], n_out ? (size_t)n_out : 1));
+            g.dst_valid[c] = j->col_validity[i];
+        }
+    }
+    HIP_TRY(hipEventRecord(ev[4], s));
+    /* every index is written by the emit; zeroed first so that no gather ever reads an
+     * index this run did not produce */
+    if (j->build_idx) HIP_TRY(hipMemsetAsync(j->build_idx, 0, idx_bytes, s));
+    if (j->probe_idx) HIP_TRY(hipMemsetAsync(j->probe_idx, 0, idx_bytes, s));
+    if (left)
+        HIP_TRY(dd_launch_join_emit_build(matched, nb_rows, anti, cnt, (uint32_t)n_out,
+                                          j->build_idx, s));
+    else
+        HIP_TRY(dd_launch_join_emit_probe(&kb, &kp, d_pseg_off, d_pseg_part, probe_n_segs,
+                                          d_base, d_log2, table, next, join_type, cnt,
+                                          (uint32_t)n_out, j->build_idx, j->probe_idx, s));
+    HIP_TRY(hipEventRecord(ev[5], s));
+    HIP_TRY(dd_launch_join_gather(&gb, j->build_idx, n_out, s));
+    HIP_TRY(dd_launch_join_gather(&gp, j->probe_idx, n_out, s));
+    HIP_TRY(hipEventRecord(ev[6], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&j->kernel_ms[0], ev[0], ev[1]);
+    (void)hipEventElapsedTime(&j->kernel_ms[1], ev[1], ev[2]);
+    (void)hipEventElapsedTime(&j->kernel_ms[2], ev[2], ev[3]);
+    (void)hipEventElapsedTime(&j->kernel_ms[3], ev[4], ev[5]);
+    (void)hipEventElapsedTime(&j->kernel_ms[4], ev[5], ev[6]);
+    *out = j.release();
+    return DD_OK;
+}
+
+extern "C" int64_t dd_joiner_n_rows(const dd_joiner *j) { return j ? j->n_rows : 0; }
+
+extern "C" dd_status dd_joiner_seg_offsets(const dd_joiner *j, int64_t *host_out) {
+    if (!j || !host_out) return set_err(DD_ERR_INVALID, "null argument");
+    memcpy(host_out, j->seg_offsets.data(), j->seg_offsets.size() * 8);
+    return DD_OK;
+}
+
+extern "C" const uint32_t *dd_joiner_build_idx(const dd_joiner *j) { return j->build_idx; }
+extern "C" const uint32_t *dd_joiner_probe_idx(const dd_joiner *j) { return j->probe_idx; }
+
+extern "C" const void *dd_joiner_col_data(const dd_joiner *j, int32_t i) {
+    return j && i >= 0 && (size_t)i < j->col_data.size() ? j->col_data[(size_t)i] : nullptr;
+}
+
+extern "C" const uint8_t *dd_joiner_col_validity(const dd_joiner *j, int32_t i) {
+    return j && i >= 0 && (size_t)i < j->col_validity.size() ? j->col_validity[(size_t)i]
+                                                             : nullptr;
+}
+
+extern "C" dd_status dd_joiner_kernel_ms(const dd_joiner *j, float *out5) {
+    if (!j || !out5) return set_err(DD_ERR_INVALID, "null argument");
+    memcpy(out5, j->kernel_ms, sizeof(j->kernel_ms));
+    return DD_OK;
+}
+
+extern "C" void dd_joiner_destroy(dd_joiner *j) { delete j; }
+
 /* ---------------- coalesce (dd_coalesce_run) ---------------- */
 
 /* task_group (network_coalesce.rs:376-400): contiguous ceil-split of producers */

@@ -47,6 +47,11 @@
 #define DD_F_SCAN_TILE 1024   /* scan: table entries per block, 4 per thread */
 #define DD_F_EMPTY 0xffffffffu
 
+/* hash join above two shuffles (dd_join.hip); the table, the segment search
+ * and the block geometry are the final merge's (DD_F_*) */
+#define DD_J_SCAN_TILE 1024    /* scan: counts per block, 4 per thread */
+#define DD_J_SUMS_THREADS 1024 /* scan: tile sums per round of the one-block middle pass */
+
 /* dtype codes mirror dd_dtype in include/dd_shuffle.h */
 enum {
     DD_KDT_U8 = 1,
@@ -120,6 +125,16 @@ struct dd_final_plan {
     int32_t ops[DD_F_MAX_AGGS];        /* DD_AGG_* read as merge ops */
     int32_t state_cols[DD_F_MAX_AGGS]; /* partial state column per aggregate */
     int32_t nn_cols[DD_F_MAX_AGGS];    /* i64 non-null-count column; unused for COUNT */
+};
+
+/* the projected columns of one side of a hash join, passed by value to k_join_gather */
+struct dd_join_gather {
+    int32_t n_cols;
+    int32_t elem[DD_KMAX_COLS];               /* 1 / 2 / 4 / 8 / 16 */
+    const void *src[DD_KMAX_COLS];
+    const uint8_t *src_valid[DD_KMAX_COLS];   /* null: the column has no validity */
+    void *dst[DD_KMAX_COLS];
+    uint8_t *dst_valid[DD_KMAX_COLS];
 };
 
 /* dictionary GC (dd_dictgc.hip): one workgroup per row tile; a tile never straddles a
@@ -309,6 +324,38 @@ hipError_t dd_launch_final_merge(const dd_kargs *a, const dd_final_plan *plan,
                                  const uint32_t *slot_gid, int64_t n_groups,
                                  uint64_t *out_keys, uint32_t *out_keynull,
                                  uint64_t *out_aggs, uint64_t *out_hi, uint64_t *out_nn,
+                                 hipStream_t s);
+/* hash join (dd_join.hip). table: the build side's regions as in the final merge; next:
+ * u32[build rows] preset to DD_F_EMPTY; the layout passed to build is the build side's, to
+ * count / emit_probe the probe side's */
+hipError_t dd_launch_join_build(const dd_kargs *b, const int64_t *seg_offsets,
+                                const int32_t *seg_part, int32_t n_segs,
+                                const uint32_t *part_base, const uint32_t *part_log2,
+                                uint32_t *table, uint32_t *next, uint32_t *err, hipStream_t s);
+hipError_t dd_launch_join_count(const dd_kargs *b, const dd_kargs *p,
+                                const int64_t *seg_offsets, const int32_t *seg_part,
+                                int32_t n_segs, const uint32_t *part_base,
+                                const uint32_t *part_log2, const uint32_t *table,
+                                const uint32_t *next, int32_t join_type, uint32_t *cnt,
+                                uint8_t *matched, hipStream_t s);
+hipError_t dd_launch_join_left_cnt(const uint8_t *matched, int64_t n, int anti, uint32_t *cnt,
+                                   hipStream_t s);
+/* cnt: n rounded up to a multiple of 4 entries, the pad zero; scanned in place. sums:
+ * tiles + 1 u64; seg_out: device int64[n_segs + 2], the last entry the exact total */
+hipError_t dd_launch_join_scan(uint32_t *cnt, int64_t n, uint64_t *sums,
+                               const int64_t *seg_offsets, int32_t n_segs, int64_t *seg_out,
+                               hipStream_t s);
+hipError_t dd_launch_join_emit_probe(const dd_kargs *b, const dd_kargs *p,
+                                     const int64_t *seg_offsets, const int32_t *seg_part,
+                                     int32_t n_segs, const uint32_t *part_base,
+                                     const uint32_t *part_log2, const uint32_t *table,
+                                     const uint32_t *next, int32_t join_type,
+                                     const uint32_t *off, uint32_t n_out, uint32_t *build_idx,
+                                     uint32_t *probe_idx, hipStream_t s);
+hipError_t dd_launch_join_emit_build(const uint8_t *matched, int64_t n, int anti,
+                                     const uint32_t *off, uint32_t n_out, uint32_t *build_idx,
+                                     hipStream_t s);
+hipError_t dd_launch_join_gather(const dd_join_gather *g, const uint32_t *idx, int64_t n_out,
                                  hipStream_t s);
 }
 

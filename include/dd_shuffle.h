@@ -673,6 +673,82 @@ dd_status dd_finalizer_kernel_ms(const dd_finalizer *f, float *out3);
 /* same seam: frees the merged rows */
 void dd_finalizer_destroy(dd_finalizer *f);
 
+/* ---------------- partitioned hash join (above two co-partitioned shuffles) ----------------
+ * HashJoinExec mode=Partitioned on two RepartitionExec Hash(keys, P) inputs that share P:
+ * tests/join.rs:116,197,279, tests/tpch_plans_test.rs:59,239,867 (Inner, LeftSemi, Left) and
+ * tests/multi_task_collect_join_repros.rs:68 (LeftSemi). DESIGN.md §19 is normative.
+ *
+ * Two device batches, each with a segment layout in the final aggregation's form (above);
+ * n_segs may differ, n_parts must be equal. "Left" is the BUILD side, as in HashJoinExec.
+ * Partition p of the build side joins partition p of the probe side and nothing else;
+ * co-partitioning is the caller's contract and is not verified.
+ *
+ * Keys: 1..4 columns per side, pairwise of one dtype out of u8, bool, i16, i32, i64, nullable;
+ * equality on the raw value; a row with a NULL in any key component matches nothing.
+ * INNER emits one row per matching (build row, probe row) pair; LEFT_SEMI / LEFT_ANTI the
+ * build rows with / without a match, RIGHT_SEMI / RIGHT_ANTI the probe rows (a NULL-key row
+ * is without a match). Output rows follow the row order of the EMITTING side (probe for
+ * INNER and RIGHT_*, build for LEFT_*) and keep its segments: the same seg_part, new
+ * seg_offsets. The matches of one probe row are adjacent, in an unspecified order.
+ *
+ * Output columns: build_proj then probe_proj (column indices; the plan's projection=[...]),
+ * fixed-width dtypes of element size 1, 2, 4, 8 or 16; an output column has a validity
+ * buffer exactly when its source has one; values and validity bytes are copied bit-exactly.
+ * A semi / anti join takes the emitting side's list only.
+ *
+ * DD_ERR_UNSUPPORTED, with a message that names the cause: f32 / f64 keys (Arrow compares
+ * float join keys by total order, the key bits here canonicalise -0.0 and NaN), dict32, utf8
+ * or dec128 keys; a var-width or dict32 column in a projection; more than 4 keys; LEFT, RIGHT
+ * and FULL; and, after the count pass, an output of 2^31 rows or more (chunk the probe
+ * side; nothing is emitted). DD_ERR_INVALID: key dtypes that differ pairwise, unequal
+ * n_parts, a malformed layout, a column index out of range, the other side's list on a semi
+ * / anti join, n_rows >= 2^31 on either side. An empty side or an empty result succeeds with
+ * zero rows and a valid layout. Synchronous on `stream`. */
+
+#define DD_JOIN_INNER 0
+#define DD_JOIN_LEFT_SEMI 1
+#define DD_JOIN_LEFT_ANTI 2
+#define DD_JOIN_RIGHT_SEMI 3
+#define DD_JOIN_RIGHT_ANTI 4
+#define DD_JOIN_LEFT 5  /* the outer joins are named so that they can be refused by name */
+#define DD_JOIN_RIGHT 6
+#define DD_JOIN_FULL 7
+
+typedef struct dd_joiner dd_joiner; /* opaque: pair indices and gathered columns */
+
+/* seam: HashJoinExec mode=Partitioned above two RepartitionExec Hash(keys, P)
+ * (tests/join.rs:116, tests/tpch_plans_test.rs:59) */
+dd_status dd_hash_join_run(const dd_batch_desc *build, const int32_t *build_keys,
+                           const dd_batch_desc *probe, const int32_t *probe_keys,
+                           int32_t n_keys, int32_t join_type,
+                           const int64_t *build_seg_offsets, const int32_t *build_seg_part,
+                           int32_t build_n_segs, int32_t build_n_parts,
+                           const int64_t *probe_seg_offsets, const int32_t *probe_seg_part,
+                           int32_t probe_n_segs, int32_t probe_n_parts,
+                           const int32_t *build_proj, int32_t n_build_proj,
+                           const int32_t *probe_proj, int32_t n_probe_proj, void *stream,
+                           dd_joiner **out);
+/* same seam: output rows of the HashJoinExec */
+int64_t dd_joiner_n_rows(const dd_joiner *j);
+/* same seam: host_out[n_segs + 1] of the emitting side: output segment s is rows
+ * [out[s], out[s + 1]) -- the partitioning the join keeps from its RepartitionExec inputs */
+dd_status dd_joiner_seg_offsets(const dd_joiner *j, int64_t *host_out);
+/* same seam: device u32[n_rows] build row of each output row (the join's left indices);
+ * NULL for RIGHT_SEMI / RIGHT_ANTI */
+const uint32_t *dd_joiner_build_idx(const dd_joiner *j);
+/* same seam: device u32[n_rows] probe row of each output row (the join's right indices);
+ * NULL for LEFT_SEMI / LEFT_ANTI */
+const uint32_t *dd_joiner_probe_idx(const dd_joiner *j);
+/* same seam: device values of output column i (build_proj first, then probe_proj): the
+ * HashJoinExec's projected output batch, columnar on the device for the next operator */
+const void *dd_joiner_col_data(const dd_joiner *j, int32_t i);
+/* same seam: device validity bytes of output column i, NULL when its source has none */
+const uint8_t *dd_joiner_col_validity(const dd_joiner *j, int32_t i);
+/* same seam: hipEvent times of the run in ms: out5 = [build, count, scan, emit, gather] */
+dd_status dd_joiner_kernel_ms(const dd_joiner *j, float *out5);
+/* same seam: frees the join's output */
+void dd_joiner_destroy(dd_joiner *j);
+
 /* ---------------- device helpers (harness convenience; not part of the seam) ------- */
 dd_status dd_dev_alloc(int64_t bytes, void **out);
 dd_status dd_dev_free(void *p);
