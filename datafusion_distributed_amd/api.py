@@ -126,6 +126,8 @@ def lib():
         L.dd_finalizer_destroy.argtypes = [ctypes.c_void_p]
         L.dd_joiner_n_rows.restype = ctypes.c_int64
         L.dd_joiner_n_rows.argtypes = [ctypes.c_void_p]
+        L.dd_joiner_n_segs.restype = ctypes.c_int32
+        L.dd_joiner_n_segs.argtypes = [ctypes.c_void_p]
         for fn in (L.dd_joiner_build_idx, L.dd_joiner_probe_idx):
             fn.restype = ctypes.c_void_p
             fn.argtypes = [ctypes.c_void_p]
@@ -1274,3 +1276,59 @@ def hash_join(build: DeviceBatch, build_keys, probe: DeviceBatch, probe_keys,
     out_cols = [(b.cols[i]["dtype"], bool(b.desc.cols[i].validity))
                 for b, proj in ((build, build_proj), (probe, probe_proj)) for i in proj]
     return Joined(h, join_type, out_cols, ppart if emits_probe else bpart, bparts)
+
+
+OUTER_JOIN_TYPES = ("left", "right", "full")
+JOIN_NONE = 0xFFFFFFFF  # DD_JOIN_NONE: the absent side of an outer join's output row
+
+
+def outer_join(build: DeviceBatch, build_keys, probe: DeviceBatch, probe_keys, join_type,
+               build_layout=None, probe_layout=None, build_proj=None, probe_proj=None):
+    """GPU partitioned outer hash join (dd_hash_join_outer_run): hash_join's
+    arguments, keys, layouts and refusals, for join_type "left", "right" or "full" (`build`
+    is HashJoinExec's left side).
+
+    "right": every inner pair plus one row per probe row without a match, build side NULL;
+    "left": every inner pair plus one row per build row no probe row matched, probe side
+    NULL; "full": both. A NULL-key row is a row without a match.
+    Returns a Joined whose segments come in two sections: the probe side's segments (rows in
+    probe row order; an unmatched probe row in its place under right / full), then for left
+    and full the build side's segments holding its unmatched rows in row order. seg_part is
+    the concatenation, n_parts unchanged. pairs() returns both arrays, JOIN_NONE marking the
+    absent side. Every column of a NULL-extended side (probe for left, build for right, both
+    for full) has validity: 0 and zero value bytes on a JOIN_NONE row.
+    build_proj / probe_proj: default all columns of both sides."""
+    if join_type not in JOIN_TYPES:
+        raise ValueError(f"outer_join: unknown join type {join_type!r}")
+    if len(build_keys) != len(probe_keys):
+        raise ValueError("outer_join: the two sides need the same number of key columns")
+    nk = len(build_keys)
+    if build_proj is None:
+        build_proj = list(range(build.desc.n_cols))
+    if probe_proj is None:
+        probe_proj = list(range(probe.desc.n_cols))
+    boff, bpart, bparts = _join_layout(build_layout, build.n_rows)
+    poff, ppart, pparts = _join_layout(probe_layout, probe.n_rows)
+    bk = (ctypes.c_int32 * max(nk, 1))(*build_keys)
+    pk = (ctypes.c_int32 * max(nk, 1))(*probe_keys)
+    bp = (ctypes.c_int32 * max(len(build_proj), 1))(*build_proj)
+    pp = (ctypes.c_int32 * max(len(probe_proj), 1))(*probe_proj)
+    h = ctypes.c_void_p()
+    # the five other types reach the library too: it refuses them and names hash_join's entry
+    _check(lib().dd_hash_join_outer_run(
+        ctypes.byref(build.desc), bk, ctypes.byref(probe.desc), pk, ctypes.c_int32(nk),
+        ctypes.c_int32(JOIN_TYPES[join_type]),
+        boff.ctypes.data_as(ctypes.c_void_p), bpart.ctypes.data_as(ctypes.c_void_p),
+        ctypes.c_int32(len(bpart)), ctypes.c_int32(bparts),
+        poff.ctypes.data_as(ctypes.c_void_p), ppart.ctypes.data_as(ctypes.c_void_p),
+        ctypes.c_int32(len(ppart)), ctypes.c_int32(pparts),
+        bp, ctypes.c_int32(len(build_proj)), pp, ctypes.c_int32(len(probe_proj)),
+        None, ctypes.byref(h)))
+    null_ext = {"left": (False, True), "right": (True, False), "full": (True, True)}[join_type]
+    out_cols = [(b.cols[i]["dtype"], ext or bool(b.desc.cols[i].validity))
+                for b, proj, ext in ((build, build_proj, null_ext[0]),
+                                     (probe, probe_proj, null_ext[1])) for i in proj]
+    seg_part = ppart if join_type == "right" else np.concatenate([ppart, bpart])
+    joined = Joined(h, join_type, out_cols, seg_part, bparts)
+    assert int(lib().dd_joiner_n_segs(h)) == len(seg_part)
+    return joined

@@ -2862,33 +2862,27 @@ static void dd_join_kargs(const dd_batch_desc *b, const int32_t *keys, int32_t n
     }
 }
 
-extern "C" dd_status dd_hash_join_run(
-    const dd_batch_desc *build, const int32_t *build_keys, const dd_batch_desc *probe,
-    const int32_t *probe_keys, int32_t n_keys, int32_t join_type,
-    const int64_t *build_seg_offsets, const int32_t *build_seg_part, int32_t build_n_segs,
-    int32_t build_n_parts, const int64_t *probe_seg_offsets, const int32_t *probe_seg_part,
-    int32_t probe_n_segs, int32_t probe_n_parts, const int32_t *build_proj,
-    int32_t n_build_proj, const int32_t *probe_proj, int32_t n_probe_proj, void *stream,
-    dd_joiner **out) {
-    if (!build || !build_keys || !probe || !probe_keys || !build_seg_offsets ||
-        !build_seg_part || !probe_seg_offsets || !probe_seg_part || !out)
-        return set_err(DD_ERR_INVALID, "hash join: null argument");
-    if (join_type == DD_JOIN_LEFT || join_type == DD_JOIN_RIGHT || join_type == DD_JOIN_FULL)
-        return set_err(DD_ERR_UNSUPPORTED, "hash join: outer joins (left, right, full) are not "
-                                           "supported");
-    if (join_type < DD_JOIN_INNER || join_type > DD_JOIN_FULL)
-        return set_err(DD_ERR_INVALID, "hash join: unknown join type");
+/* what dd_hash_join_run and dd_hash_join_outer_run check alike, all before any device
+ * work: key count, both sides' keys and projections, both layouts, co-partitioning; and the
+ * table regions from the BUILD side's rows per partition (the final merge's sizing) */
+struct dd_join_regions {
+    std::vector<uint32_t> base, log2;
+    uint64_t n_slots = 0;
+};
+
+static dd_status dd_join_check_n_keys(int32_t n_keys) {
     if (n_keys > 4) return set_err(DD_ERR_UNSUPPORTED, "hash join: more than 4 key columns");
     if (n_keys < 1) return set_err(DD_ERR_INVALID, "hash join: at least 1 key column");
-    const bool left = join_type == DD_JOIN_LEFT_SEMI || join_type == DD_JOIN_LEFT_ANTI;
-    const bool right = join_type == DD_JOIN_RIGHT_SEMI || join_type == DD_JOIN_RIGHT_ANTI;
-    const bool anti = join_type == DD_JOIN_LEFT_ANTI || join_type == DD_JOIN_RIGHT_ANTI;
-    if (left && n_probe_proj != 0)
-        return set_err(DD_ERR_INVALID, "hash join: a left_semi / left_anti join emits build "
-                                       "rows: a probe-side projection list is not allowed");
-    if (right && n_build_proj != 0)
-        return set_err(DD_ERR_INVALID, "hash join: a right_semi / right_anti join emits probe "
-                                       "rows: a build-side projection list is not allowed");
+    return DD_OK;
+}
+
+static dd_status dd_join_check_inputs(
+    const dd_batch_desc *build, const int32_t *build_keys, const dd_batch_desc *probe,
+    const int32_t *probe_keys, int32_t n_keys, const int64_t *build_seg_offsets,
+    const int32_t *build_seg_part, int32_t build_n_segs, int32_t build_n_parts,
+    const int64_t *probe_seg_offsets, const int32_t *probe_seg_part, int32_t probe_n_segs,
+    int32_t probe_n_parts, const int32_t *build_proj, int32_t n_build_proj,
+    const int32_t *probe_proj, int32_t n_probe_proj, dd_join_regions *reg) {
     dd_status st = dd_join_check_side("build side:", build, build_keys, n_keys, build_proj,
                                       n_build_proj);
     if (st != DD_OK) return st;
@@ -2911,16 +2905,55 @@ extern "C" dd_status dd_hash_join_run(
         return set_err(DD_ERR_INVALID, "hash join: unequal n_parts: the two sides must be "
                                        "co-partitioned");
     const int32_t n_parts = build_n_parts;
-    /* table regions from the BUILD side's rows per partition (the final merge's sizing) */
-    std::vector<uint32_t> base_h((size_t)n_parts), log2_h((size_t)n_parts);
-    uint64_t n_slots = 0;
-    for (int p = 0; p < n_parts && n_slots < ((uint64_t)1 << 32); p++) {
-        log2_h[p] = dd_final_region_log2(rows_b[p]);
-        base_h[p] = (uint32_t)n_slots;
-        n_slots += (uint64_t)1 << log2_h[p];
+    reg->base.assign((size_t)n_parts, 0);
+    reg->log2.assign((size_t)n_parts, 0);
+    reg->n_slots = 0;
+    for (int p = 0; p < n_parts && reg->n_slots < ((uint64_t)1 << 32); p++) {
+        reg->log2[p] = dd_final_region_log2(rows_b[p]);
+        reg->base[p] = (uint32_t)reg->n_slots;
+        reg->n_slots += (uint64_t)1 << reg->log2[p];
     }
-    if (n_slots >= ((uint64_t)1 << 32))
+    if (reg->n_slots >= ((uint64_t)1 << 32))
         return set_err(DD_ERR_UNSUPPORTED, "hash join: build table past 2^32 slots");
+    return DD_OK;
+}
+
+extern "C" dd_status dd_hash_join_run(
+    const dd_batch_desc *build, const int32_t *build_keys, const dd_batch_desc *probe,
+    const int32_t *probe_keys, int32_t n_keys, int32_t join_type,
+    const int64_t *build_seg_offsets, const int32_t *build_seg_part, int32_t build_n_segs,
+    int32_t build_n_parts, const int64_t *probe_seg_offsets, const int32_t *probe_seg_part,
+    int32_t probe_n_segs, int32_t probe_n_parts, const int32_t *build_proj,
+    int32_t n_build_proj, const int32_t *probe_proj, int32_t n_probe_proj, void *stream,
+    dd_joiner **out) {
+    if (!build || !build_keys || !probe || !probe_keys || !build_seg_offsets ||
+        !build_seg_part || !probe_seg_offsets || !probe_seg_part || !out)
+        return set_err(DD_ERR_INVALID, "hash join: null argument");
+    if (join_type == DD_JOIN_LEFT || join_type == DD_JOIN_RIGHT || join_type == DD_JOIN_FULL)
+        return set_err(DD_ERR_UNSUPPORTED, "hash join: outer joins (left, right, full) are not "
+                                           "supported");
+    if (join_type < DD_JOIN_INNER || join_type > DD_JOIN_FULL)
+        return set_err(DD_ERR_INVALID, "hash join: unknown join type");
+    dd_status st = dd_join_check_n_keys(n_keys);
+    if (st != DD_OK) return st;
+    const bool left = join_type == DD_JOIN_LEFT_SEMI || join_type == DD_JOIN_LEFT_ANTI;
+    const bool right = join_type == DD_JOIN_RIGHT_SEMI || join_type == DD_JOIN_RIGHT_ANTI;
+    const bool anti = join_type == DD_JOIN_LEFT_ANTI || join_type == DD_JOIN_RIGHT_ANTI;
+    if (left && n_probe_proj != 0)
+        return set_err(DD_ERR_INVALID, "hash join: a left_semi / left_anti join emits build "
+                                       "rows: a probe-side projection list is not allowed");
+    if (right && n_build_proj != 0)
+        return set_err(DD_ERR_INVALID, "hash join: a right_semi / right_anti join emits probe "
+                                       "rows: a build-side projection list is not allowed");
+    dd_join_regions reg;
+    st = dd_join_check_inputs(build, build_keys, probe, probe_keys, n_keys, build_seg_offsets,
+                              build_seg_part, build_n_segs, build_n_parts, probe_seg_offsets,
+                              probe_seg_part, probe_n_segs, probe_n_parts, build_proj,
+                              n_build_proj, probe_proj, n_probe_proj, &reg);
+    if (st != DD_OK) return st;
+    const int32_t n_parts = build_n_parts;
+    const std::vector<uint32_t> &base_h = reg.base, &log2_h = reg.log2;
+    const uint64_t n_slots = reg.n_slots;
 
     const int64_t nb_rows = build->n_rows, np_rows = probe->n_rows;
     /* the emitting side: its rows are scanned, its segments are kept */
@@ -3067,7 +3100,197 @@ extern "C" dd_status dd_hash_join_run(
     return DD_OK;
 }
 
+/* ---------------- outer joins: left, right, full ---------------- */
+
+extern "C" dd_status dd_hash_join_outer_run(
+    const dd_batch_desc *build, const int32_t *build_keys, const dd_batch_desc *probe,
+    const int32_t *probe_keys, int32_t n_keys, int32_t join_type,
+    const int64_t *build_seg_offsets, const int32_t *build_seg_part, int32_t build_n_segs,
+    int32_t build_n_parts, const int64_t *probe_seg_offsets, const int32_t *probe_seg_part,
+    int32_t probe_n_segs, int32_t probe_n_parts, const int32_t *build_proj,
+    int32_t n_build_proj, const int32_t *probe_proj, int32_t n_probe_proj, void *stream,
+    dd_joiner **out) {
+    if (!build || !build_keys || !probe || !probe_keys || !build_seg_offsets ||
+        !build_seg_part || !probe_seg_offsets || !probe_seg_part || !out)
+        return set_err(DD_ERR_INVALID, "hash join: null argument");
+    if (join_type < DD_JOIN_INNER || join_type > DD_JOIN_FULL)
+        return set_err(DD_ERR_INVALID, "outer join: unknown join type");
+    if (join_type != DD_JOIN_LEFT && join_type != DD_JOIN_RIGHT && join_type != DD_JOIN_FULL)
+        return set_err(DD_ERR_INVALID, "outer join: inner, semi and anti joins are "
+                                       "dd_hash_join_run's; this entry takes left, right and "
+                                       "full");
+    dd_status st = dd_join_check_n_keys(n_keys);
+    if (st != DD_OK) return st;
+    dd_join_regions reg;
+    st = dd_join_check_inputs(build, build_keys, probe, probe_keys, n_keys, build_seg_offsets,
+                              build_seg_part, build_n_segs, build_n_parts, probe_seg_offsets,
+                              probe_seg_part, probe_n_segs, probe_n_parts, build_proj,
+                              n_build_proj, probe_proj, n_probe_proj, &reg);
+    if (st != DD_OK) return st;
+    const int32_t n_parts = build_n_parts;
+    /* keep_probe: probe rows without a match come out with the build side NULL; keep_build:
+     * the unmatched build rows follow in a second section with the probe side NULL */
+    const bool keep_probe = join_type != DD_JOIN_LEFT, keep_build = join_type != DD_JOIN_RIGHT;
+    const int64_t nb_rows = build->n_rows, np_rows = probe->n_rows;
+    const int64_t n_tail = keep_build ? nb_rows : 0;
+    const int64_t n_scan = np_rows + n_tail; /* < 2^32 */
+    const int32_t o_n_segs = probe_n_segs + (keep_build ? build_n_segs : 0);
+    const int n_out_cols = n_build_proj + n_probe_proj;
+
+    auto j = std::unique_ptr<dd_joiner>(new dd_joiner());
+    j->seg_offsets.assign((size_t)o_n_segs + 1, 0);
+    j->col_data.assign((size_t)n_out_cols, nullptr);
+    j->col_validity.assign((size_t)n_out_cols, nullptr);
+    /* nothing can come out: a right join without probe rows, any join of two empty sides */
+    if (n_scan == 0) {
+        *out = j.release();
+        return DD_OK;
+    }
+    if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
+
+    /* the scan's boundaries over cnt[np_rows + n_tail]: the probe segments, then the build
+     * segments shifted behind the probe rows */
+    std::vector<int64_t> oseg_h((size_t)o_n_segs + 1);
+    for (int s = 0; s <= probe_n_segs; s++) oseg_h[(size_t)s] = probe_seg_offsets[s];
+    if (keep_build)
+        for (int s = 1; s <= build_n_segs; s++)
+            oseg_h[(size_t)probe_n_segs + s] = np_rows + build_seg_offsets[s];
+
+    dd_kargs kb, kp;
+    dd_join_kargs(build, build_keys, n_keys, &kb);
+    dd_join_kargs(probe, probe_keys, n_keys, &kp);
+
+    hipStream_t s = (hipStream_t)stream;
+    dd_dev_scratch ws;
+    int64_t *d_bseg_off = nullptr, *d_pseg_off = nullptr, *d_oseg_off = nullptr,
+            *d_seg_out = nullptr;
+    int32_t *d_bseg_part = nullptr, *d_pseg_part = nullptr;
+    uint32_t *d_base = nullptr, *d_log2 = nullptr, *table = nullptr, *next = nullptr,
+             *cnt = nullptr, *head = nullptr, *err = nullptr;
+    uint64_t *sums = nullptr;
+    uint8_t *matched = nullptr;
+    const size_t n_pad = ((size_t)n_scan + 3) & ~(size_t)3;
+    const size_t nb = (n_pad + DD_J_SCAN_TILE - 1) / DD_J_SCAN_TILE;
+    if (!ws.alloc(&d_bseg_off, ((size_t)build_n_segs + 1) * 8) ||
+        !ws.alloc(&d_bseg_part, (size_t)build_n_segs * 4) ||
+        !ws.alloc(&d_pseg_off, ((size_t)probe_n_segs + 1) * 8) ||
+        !ws.alloc(&d_pseg_part, (size_t)probe_n_segs * 4) ||
+        !ws.alloc(&d_oseg_off, ((size_t)o_n_segs + 1) * 8) ||
+        !ws.alloc(&d_seg_out, ((size_t)o_n_segs + 2) * 8) ||
+        !ws.alloc(&d_base, (size_t)n_parts * 4) || !ws.alloc(&d_log2, (size_t)n_parts * 4) ||
+        !ws.alloc(&table, (size_t)reg.n_slots * 4) || !ws.alloc(&next, (size_t)nb_rows * 4) ||
+        !ws.alloc(&cnt, n_pad * 4) || !ws.alloc(&head, (size_t)np_rows * 4) ||
+        !ws.alloc(&sums, (nb + 1) * 8) || !ws.alloc(&err, 4) ||
+        (keep_build && !ws.alloc(&matched, (size_t)nb_rows)))
+        return set_err(DD_ERR_HIP, "outer join: workspace alloc");
+    hipEvent_t ev[7] = {};
+    struct ev_guard {
+        hipEvent_t *e;
+        ~ev_guard() {
+            for (int i = 0; i < 7; i++)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } evg{ev};
+    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemcpyAsync(d_bseg_off, build_seg_offsets, ((size_t)build_n_segs + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_bseg_part, build_seg_part, (size_t)build_n_segs * 4,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_pseg_off, probe_seg_offsets, ((size_t)probe_n_segs + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_pseg_part, probe_seg_part, (size_t)probe_n_segs * 4,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_oseg_off, oseg_h.data(), ((size_t)o_n_segs + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_base, reg.base.data(), (size_t)n_parts * 4,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_log2, reg.log2.data(), (size_t)n_parts * 4,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(err, 0, 4, s));
+    /* pageable host sources: the copies have left them before anything else happens */
+    HIP_TRY(hipStreamSynchronize(s));
+
+    HIP_TRY(hipEventRecord(ev[0], s));
+    HIP_TRY(hipMemsetAsync(table, 0xff, (size_t)reg.n_slots * 4, s)); /* DD_F_EMPTY */
+    if (nb_rows) HIP_TRY(hipMemsetAsync(next, 0xff, (size_t)nb_rows * 4, s));
+    HIP_TRY(dd_launch_join_build(&kb, d_bseg_off, d_bseg_part, build_n_segs, d_base, d_log2,
+                                 table, next, err, s));
+    HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(hipMemsetAsync(cnt, 0, n_pad * 4, s));
+    if (keep_build && nb_rows) HIP_TRY(hipMemsetAsync(matched, 0, (size_t)nb_rows, s));
+    HIP_TRY(dd_launch_join_count_outer(&kb, &kp, d_pseg_off, d_pseg_part, probe_n_segs, d_base,
+                                       d_log2, table, next, keep_probe, head, cnt, matched,
+                                       s));
+    if (keep_build) HIP_TRY(dd_launch_join_build_cnt_outer(matched, nb_rows, np_rows, cnt, s));
+    HIP_TRY(hipEventRecord(ev[2], s));
+    HIP_TRY(dd_launch_join_scan(cnt, n_scan, sums, d_oseg_off, o_n_segs, d_seg_out, s));
+    HIP_TRY(hipEventRecord(ev[3], s));
+    /* the one mid-run sync: the output is sized by the result */
+    std::vector<int64_t> seg_out_h((size_t)o_n_segs + 2);
+    uint32_t err_h = 0;
+    HIP_TRY(hipMemcpyAsync(seg_out_h.data(), d_seg_out, ((size_t)o_n_segs + 2) * 8,
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&err_h, err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err_h) return set_err(DD_ERR_HIP, "outer join: build table overflow (internal)");
+    const uint64_t total = (uint64_t)seg_out_h[(size_t)o_n_segs + 1];
+    if (total >= ((uint64_t)1 << 31))
+        return set_err(DD_ERR_UNSUPPORTED, "outer join: output of " + std::to_string(total) +
+                                               " rows is 2^31 or more: chunk the probe side");
+    const int64_t n_out = (int64_t)total;
+    j->n_rows = n_out;
+    memcpy(j->seg_offsets.data(), seg_out_h.data(), ((size_t)o_n_segs + 1) * 8);
+
+    const size_t idx_bytes = n_out ? (size_t)n_out * 4 : 1;
+    HIP_TRY(hipMalloc((void **)&j->build_idx, idx_bytes));
+    HIP_TRY(hipMalloc((void **)&j->probe_idx, idx_bytes));
+    dd_join_gather gb, gp;
+    memset(&gb, 0, sizeof(gb));
+    memset(&gp, 0, sizeof(gp));
+    for (int i = 0; i < n_out_cols; i++) {
+        const bool from_build = i < n_build_proj;
+        const dd_col_desc &cd = from_build ? build->cols[build_proj[i]]
+                                           : probe->cols[probe_proj[i - n_build_proj]];
+        dd_join_gather &g = from_build ? gb : gp;
+        const int c = g.n_cols++;
+        g.elem[c] = fixed_elem_size(cd.dtype);
+        g.src[c] = cd.data;
+        g.src_valid[c] = (const uint8_t *)cd.validity;
+        HIP_TRY(hipMalloc(&j->col_data[i], n_out ? (size_t)n_out * g.elem[c] : 1));
+        g.dst[c] = j->col_data[i];
+        /* a NULL-extended side (build when probe rows are kept, probe when build rows are)
+         * always carries validity */
+        if (cd.validity || (from_build ? keep_probe : keep_build)) {
+            HIP_TRY(hipMalloc((void **)&j->col_validity[i], n_out ? (size_t)n_out : 1));
+            g.dst_valid[c] = j->col_validity[i];
+        }
+    }
+    HIP_TRY(hipEventRecord(ev[4], s));
+    /* every index is written by the emit; preset to DD_JOIN_NONE first, which the gather
+     * never follows, so that no gather reads an index this run did not produce */
+    HIP_TRY(hipMemsetAsync(j->build_idx, 0xff, idx_bytes, s));
+    HIP_TRY(hipMemsetAsync(j->probe_idx, 0xff, idx_bytes, s));
+    HIP_TRY(dd_launch_join_emit_outer(head, next, matched, cnt, np_rows, n_tail, keep_probe,
+                                      (uint32_t)n_out, j->build_idx, j->probe_idx, s));
+    HIP_TRY(hipEventRecord(ev[5], s));
+    HIP_TRY(dd_launch_join_gather_outer(&gb, j->build_idx, n_out, s));
+    HIP_TRY(dd_launch_join_gather_outer(&gp, j->probe_idx, n_out, s));
+    HIP_TRY(hipEventRecord(ev[6], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&j->kernel_ms[0], ev[0], ev[1]);
+    (void)hipEventElapsedTime(&j->kernel_ms[1], ev[1], ev[2]);
+    (void)hipEventElapsedTime(&j->kernel_ms[2], ev[2], ev[3]);
+    (void)hipEventElapsedTime(&j->kernel_ms[3], ev[4], ev[5]);
+    (void)hipEventElapsedTime(&j->kernel_ms[4], ev[5], ev[6]);
+    *out = j.release();
+    return DD_OK;
+}
+
 extern "C" int64_t dd_joiner_n_rows(const dd_joiner *j) { return j ? j->n_rows : 0; }
+
+extern "C" int32_t dd_joiner_n_segs(const dd_joiner *j) {
+    return j ? (int32_t)j->seg_offsets.size() - 1 : 0;
+}
 
 extern "C" dd_status dd_joiner_seg_offsets(const dd_joiner *j, int64_t *host_out) {
     if (!j || !host_out) return set_err(DD_ERR_INVALID, "null argument");

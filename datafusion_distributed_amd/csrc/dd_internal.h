@@ -357,6 +357,24 @@ hipError_t dd_launch_join_emit_build(const uint8_t *matched, int64_t n, int anti
                                      hipStream_t s);
 hipError_t dd_launch_join_gather(const dd_join_gather *g, const uint32_t *idx, int64_t n_out,
                                  hipStream_t s);
+/* outer joins. cnt: u32[n_probe + n_build] (right: [n_probe]), padded to 4
+ * as for the scan; head: u32[probe rows]; matched: u8[build rows] zeroed, null for right.
+ * emit: n_tail = build rows for left / full, 0 for right; off is the scanned cnt */
+hipError_t dd_launch_join_count_outer(const dd_kargs *b, const dd_kargs *p,
+                                      const int64_t *seg_offsets, const int32_t *seg_part,
+                                      int32_t n_segs, const uint32_t *part_base,
+                                      const uint32_t *part_log2, const uint32_t *table,
+                                      const uint32_t *next, int keep_probe, uint32_t *head,
+                                      uint32_t *cnt, uint8_t *matched, hipStream_t s);
+hipError_t dd_launch_join_build_cnt_outer(const uint8_t *matched, int64_t n_build,
+                                          int64_t n_probe, uint32_t *cnt, hipStream_t s);
+hipError_t dd_launch_join_emit_outer(const uint32_t *head, const uint32_t *next,
+                                     const uint8_t *matched, const uint32_t *off,
+                                     int64_t n_probe, int64_t n_tail, int keep_probe,
+                                     uint32_t n_out, uint32_t *build_idx, uint32_t *probe_idx,
+                                     hipStream_t s);
+hipError_t dd_launch_join_gather_outer(const dd_join_gather *g, const uint32_t *idx,
+                                       int64_t n_out, hipStream_t s);
 }
 
 #endif

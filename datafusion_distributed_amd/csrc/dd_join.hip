@@ -18,7 +18,16 @@
  *                       exact before the host range-checks it.
  *   k_join_seg_out      output seg_offsets = the scan at the emitting side's boundaries.
  *   k_join_emit_*       re-walk and write the pair indices / selected row ids.
- *   k_join_gather       out[c][i] = src[c][idx[i]] for the projected columns + validity. */
+ *   k_join_gather       out[c][i] = src[c][idx[i]] for the projected columns + validity.
+ *
+ * The outer joins (left, right, full) share build, scan and seg_out and add:
+ *   k_join_count_outer  per probe row: probe once, keep the chain head in head[row], count
+ *                       the chain, mark matched[build row] (left, full).
+ *   k_join_build_cnt_outer  left, full: cnt[n_probe + r] = !matched[r], behind the probe rows'
+ *                       counts in the one array the scan runs over.
+ *   k_join_emit_outer   probe section from head / off / next alone (no re-probe), then the
+ *                       unmatched build rows; DD_JOIN_NONE marks the absent side.
+ *   k_join_gather_outer k_join_gather that writes zeros and validity 0 on a NONE index. */
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -488,5 +497,188 @@ extern "C" hipError_t dd_launch_join_gather(const dd_join_gather *g, const uint3
     if (n_out == 0 || g->n_cols == 0) return hipSuccess;
     hipLaunchKernelGGL(k_join_gather, dim3((unsigned)((n_out + J_THREADS - 1) / J_THREADS)),
                        dim3(J_THREADS), 0, s, *g, idx, n_out);
+    return hipGetLastError();
+}
+
+/* ---------------- outer joins: left, right, full ----------------
+ * Output rows come in two sections over ONE count array cnt[n_probe + n_build]: the probe
+ * rows' pairs (right, full: at least one row each), then for left / full the build rows no
+ * probe row matched. The build part starts at index n_probe with no alignment padding, so
+ * one scan serves both; every index into cnt is 64-bit. */
+
+#define J_NONE 0xffffffffu /* DD_JOIN_NONE: the absent side of an output row */
+
+template <bool STAGED>
+__global__ __launch_bounds__(J_THREADS) void k_join_count_outer(
+    dd_kargs b, dd_kargs p, const int64_t *seg_offsets, const int32_t *seg_part,
+    int32_t n_segs, const uint32_t *part_base, const uint32_t *part_log2,
+    const uint32_t *table, const uint32_t *next, uint32_t keep_probe /* right, full */,
+    uint32_t *head_out /* [probe rows] */, uint32_t *cnt /* [probe rows] */,
+    uint8_t *matched /* [build rows]; left, full only, else null */) {
+    __shared__ int64_t s_off[STAGED ? DD_F_LDS_SEGS + 1 : 1];
+    if (STAGED) {
+        for (int i = threadIdx.x; i <= n_segs; i += J_THREADS) s_off[i] = seg_offsets[i];
+        __syncthreads();
+    }
+    const int nk = p.n_keys > J_MAXK ? J_MAXK : p.n_keys;
+    const int64_t start = (int64_t)blockIdx.x * DD_F_BLOCK_ROWS;
+    const int64_t end = start + DD_F_BLOCK_ROWS < p.n_rows ? start + DD_F_BLOCK_ROWS : p.n_rows;
+    const uint32_t max_steps = (uint32_t)b.n_rows; /* a chain is no longer than the side */
+
+    for (int64_t row = start + threadIdx.x; row < end; row += J_THREADS) {
+        const uint32_t head = j_probe<STAGED>(b, p, nk, row, s_off, seg_offsets, seg_part,
+                                              n_segs, part_base, part_log2, table);
+        head_out[row] = head; /* the emit walks from here: it never probes again */
+        uint32_t c = 0;
+        if (matched) {
+            /* idempotent byte stores; unlike left_semi the walk cannot stop at a marked
+             * head, the count is needed. Nobody reads `matched` before this kernel ends */
+            for (uint32_t r = head; r != J_EMPTY && c < max_steps; r = next[r], c++)
+                if (!matched[r]) matched[r] = 1;
+        } else {
+            for (uint32_t r = head; r != J_EMPTY && c < max_steps; r = next[r]) c++;
+        }
+        cnt[row] = keep_probe && c == 0 ? 1u : c;
+    }
+}
+
+extern "C" hipError_t dd_launch_join_count_outer(
+    const dd_kargs *b, const dd_kargs *p, const int64_t *seg_offsets, const int32_t *seg_part,
+    int32_t n_segs, const uint32_t *part_base, const uint32_t *part_log2,
+    const uint32_t *table, const uint32_t *next, int keep_probe, uint32_t *head,
+    uint32_t *cnt, uint8_t *matched, hipStream_t s) {
+    const int64_t nblocks = (p->n_rows + DD_F_BLOCK_ROWS - 1) / DD_F_BLOCK_ROWS;
+    if (nblocks == 0) return hipSuccess;
+    if (n_segs <= DD_F_LDS_SEGS)
+        hipLaunchKernelGGL(k_join_count_outer<true>, dim3((unsigned)nblocks), dim3(J_THREADS),
+                           0, s, *b, *p, seg_offsets, seg_part, n_segs, part_base, part_log2,
+                           table, next, (uint32_t)(keep_probe != 0), head, cnt, matched);
+    else
+        hipLaunchKernelGGL(k_join_count_outer<false>, dim3((unsigned)nblocks), dim3(J_THREADS),
+                           0, s, *b, *p, seg_offsets, seg_part, n_segs, part_base, part_log2,
+                           table, next, (uint32_t)(keep_probe != 0), head, cnt, matched);
+    return hipGetLastError();
+}
+
+/* left, full: the build rows' counts, behind the probe rows' in the same array */
+__global__ __launch_bounds__(J_THREADS) void k_join_build_cnt_outer(const uint8_t *matched,
+                                                                    int64_t n_build,
+                                                                    uint64_t n_probe,
+                                                                    uint32_t *cnt) {
+    const int64_t r = (int64_t)blockIdx.x * J_THREADS + threadIdx.x;
+    if (r < n_build) cnt[n_probe + (uint64_t)r] = matched[r] == 0;
+}
+
+extern "C" hipError_t dd_launch_join_build_cnt_outer(const uint8_t *matched, int64_t n_build,
+                                                     int64_t n_probe, uint32_t *cnt,
+                                                     hipStream_t s) {
+    if (n_build == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_join_build_cnt_outer,
+                       dim3((unsigned)((n_build + J_THREADS - 1) / J_THREADS)), dim3(J_THREADS),
+                       0, s, matched, n_build, (uint64_t)n_probe, cnt);
+    return hipGetLastError();
+}
+
+/* one entry of cnt per thread. Probe section: walk next from the stored head and write the
+ * pairs at off[row] + k, or (NONE, row) for a kept row without a match. Build section (n_tail
+ * = build rows for left / full, else 0): (r, NONE) for the rows nobody marked. No key loads,
+ * no table, no segment search, hence no dd_kargs. Every store is below n_out. */
+__global__ __launch_bounds__(J_THREADS) void k_join_emit_outer(
+    const uint32_t *head, const uint32_t *next, const uint8_t *matched,
+    const uint32_t *off /* [n_probe + n_tail] exclusive scan of cnt */, uint64_t n_probe,
+    uint64_t n_tail, uint32_t keep_probe, uint32_t n_out, uint32_t *build_idx,
+    uint32_t *probe_idx) {
+    const uint64_t i = (uint64_t)blockIdx.x * J_THREADS + threadIdx.x;
+    if (i >= n_probe + n_tail) return;
+    uint32_t o = off[i];
+    if (i < n_probe) {
+        uint32_t r = head[i];
+        if (r == J_EMPTY) {
+            if (keep_probe && o < n_out) {
+                build_idx[o] = J_NONE;
+                probe_idx[o] = (uint32_t)i;
+            }
+            return;
+        }
+        /* o < n_out bounds the walk by what the count pass found */
+        for (; r != J_EMPTY && o < n_out; r = next[r], o++) {
+            build_idx[o] = r;
+            probe_idx[o] = (uint32_t)i;
+        }
+    } else {
+        const uint64_t r = i - n_probe;
+        if (!matched[r] && o < n_out) {
+            build_idx[o] = (uint32_t)r;
+            probe_idx[o] = J_NONE;
+        }
+    }
+}
+
+extern "C" hipError_t dd_launch_join_emit_outer(const uint32_t *head, const uint32_t *next,
+                                                const uint8_t *matched, const uint32_t *off,
+                                                int64_t n_probe, int64_t n_tail,
+                                                int keep_probe, uint32_t n_out,
+                                                uint32_t *build_idx, uint32_t *probe_idx,
+                                                hipStream_t s) {
+    const uint64_t n = (uint64_t)n_probe + (uint64_t)n_tail; /* < 2^32: blocks < 2^24 */
+    if (n == 0 || n_out == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_join_emit_outer, dim3((unsigned)((n + J_THREADS - 1) / J_THREADS)),
+                       dim3(J_THREADS), 0, s, head, next, matched, off, (uint64_t)n_probe,
+                       (uint64_t)n_tail, (uint32_t)(keep_probe != 0), n_out, build_idx,
+                       probe_idx);
+    return hipGetLastError();
+}
+
+/* k_join_gather for a side whose index may be NONE: the source is not read then, the value
+ * bytes are zero and the validity byte 0. dst_valid[c] decides whether validity is written:
+ * always set on a NULL-extended side (1 on a real row of a source without validity), set
+ * exactly where the source has one on the other side, whose index is never NONE */
+__global__ __launch_bounds__(J_THREADS) void k_join_gather_outer(dd_join_gather g,
+                                                                 const uint32_t *idx,
+                                                                 int64_t n_out) {
+    const int64_t i = (int64_t)blockIdx.x * J_THREADS + threadIdx.x;
+    if (i >= n_out) return;
+    const uint32_t src = idx[i];
+    const bool real = src != J_NONE;
+    for (int c0 = 0; c0 < g.n_cols; c0 += J_GATHER_GROUP) {
+        dd_u128 v[J_GATHER_GROUP];
+        uint8_t ok[J_GATHER_GROUP];
+#pragma unroll
+        for (int j = 0; j < J_GATHER_GROUP; j++) {
+            const int c = c0 + j;
+            v[j] = dd_u128{0, 0};
+            ok[j] = 0;
+            if (c >= g.n_cols || !real) continue;
+            switch (g.elem[c]) { /* wave-uniform */
+            case 1: j_ld<uint8_t>(v[j], g.src[c], src); break;
+            case 2: j_ld<uint16_t>(v[j], g.src[c], src); break;
+            case 4: j_ld<uint32_t>(v[j], g.src[c], src); break;
+            case 8: j_ld<uint64_t>(v[j], g.src[c], src); break;
+            default: v[j] = ((const dd_u128 *)g.src[c])[src];
+            }
+            ok[j] = g.src_valid[c] ? g.src_valid[c][src] : (uint8_t)1;
+        }
+#pragma unroll
+        for (int j = 0; j < J_GATHER_GROUP; j++) {
+            const int c = c0 + j;
+            if (c >= g.n_cols) continue;
+            switch (g.elem[c]) {
+            case 1: ((uint8_t *)g.dst[c])[i] = (uint8_t)v[j].x; break;
+            case 2: ((uint16_t *)g.dst[c])[i] = (uint16_t)v[j].x; break;
+            case 4: ((uint32_t *)g.dst[c])[i] = (uint32_t)v[j].x; break;
+            case 8: ((uint64_t *)g.dst[c])[i] = v[j].x; break;
+            default: ((dd_u128 *)g.dst[c])[i] = v[j];
+            }
+            if (g.dst_valid[c]) g.dst_valid[c][i] = ok[j];
+        }
+    }
+}
+
+extern "C" hipError_t dd_launch_join_gather_outer(const dd_join_gather *g, const uint32_t *idx,
+                                                  int64_t n_out, hipStream_t s) {
+    if (n_out == 0 || g->n_cols == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_join_gather_outer,
+                       dim3((unsigned)((n_out + J_THREADS - 1) / J_THREADS)), dim3(J_THREADS),
+                       0, s, *g, idx, n_out);
     return hipGetLastError();
 }

@@ -10,6 +10,9 @@ The output follows the EMITTING side (probe for inner / right_*, build for left_
 order, and its segments with new offsets. hash_join_ref returns, per segment of that side,
 the list of (build_row, probe_row) pairs (inner; a probe row's matches adjacent, here in
 ascending build row, which the kernels do not promise) or of row ids (semi / anti).
+
+The outer joins (left, right, full) have a model of their own,
+outer_join_ref: their output has two sections of segments and pairs with an absent side.
 """
 
 import numpy as np
@@ -18,6 +21,7 @@ from datafusion_distributed_amd import finalagg
 from oracle import reduce_ref as rr
 
 JOIN_TYPES = ("inner", "left_semi", "left_anti", "right_semi", "right_anti")
+OUTER_JOIN_TYPES = ("left", "right", "full")  # outer_join_ref, DESIGN.md §20
 KEY_DTYPES = ("u8", "bool", "i16", "i32", "i64")
 
 
@@ -96,6 +100,56 @@ def hash_join_ref(build_cols, build_keys, probe_cols, probe_keys, join_type="inn
             if hit == (join_type == "left_semi"):
                 seg.append(r)
         out.append(seg)
+    return out
+
+
+def outer_join_ref(build_cols, build_keys, probe_cols, probe_keys, join_type,
+                   build_layout=None, probe_layout=None):
+    """The outer joins of DESIGN.md §20: one list per OUTPUT segment of
+    (build_row | None, probe_row | None).
+
+    Section 1, the probe side's segments: per probe row, in row order, its inner pairs (in
+    ascending build row, which the kernels do not promise) or, for right / full, one
+    (None, row) when it has none. Section 2, left / full only, the build side's segments:
+    the build rows no probe row matched, in row order, as (row, None). A NULL-key row is a
+    row without a match."""
+    if join_type not in OUTER_JOIN_TYPES:
+        raise ValueError(f"outer join: unknown or unsupported join type {join_type!r} "
+                         "(hash_join_ref serves the others)")
+    if not 1 <= len(build_keys) <= 4 or len(build_keys) != len(probe_keys):
+        raise ValueError("outer join: 1..4 key columns per side")
+    for b, p in zip(build_keys, probe_keys):
+        if build_cols[b]["dtype"] != probe_cols[p]["dtype"]:
+            raise ValueError("outer join: key dtypes differ pairwise")
+    _, boff, bpart, bparts, bid = _side(build_cols, build_keys, build_layout)
+    _, poff, ppart, pparts, pid = _side(probe_cols, probe_keys, probe_layout)
+    if bparts != pparts:
+        raise ValueError("outer join: n_parts of the two sides differ")
+
+    tables = []
+    for rows in finalagg.partition_rows(boff, bpart, bparts):
+        t = {}
+        for r in rows.tolist():
+            if bid[r] is not None:
+                t.setdefault(bid[r], []).append(r)
+        tables.append(t)
+
+    keep_probe = join_type in ("right", "full")
+    matched = set()
+    out = []
+    for s, p in enumerate(ppart.tolist()):
+        seg = []
+        for r in range(int(poff[s]), int(poff[s + 1])):
+            hits = tables[p].get(pid[r], ()) if pid[r] is not None else ()
+            seg.extend((b, r) for b in hits)
+            matched.update(hits)
+            if not hits and keep_probe:
+                seg.append((None, r))
+        out.append(seg)
+    if join_type in ("left", "full"):
+        for s in range(len(bpart)):
+            out.append([(r, None) for r in range(int(boff[s]), int(boff[s + 1]))
+                        if r not in matched])
     return out
 
 

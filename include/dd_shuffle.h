@@ -710,7 +710,7 @@ void dd_finalizer_destroy(dd_finalizer *f);
 #define DD_JOIN_LEFT_ANTI 2
 #define DD_JOIN_RIGHT_SEMI 3
 #define DD_JOIN_RIGHT_ANTI 4
-#define DD_JOIN_LEFT 5  /* the outer joins are named so that they can be refused by name */
+#define DD_JOIN_LEFT 5  /* the outer joins: refused here by name, dd_hash_join_outer_run's */
 #define DD_JOIN_RIGHT 6
 #define DD_JOIN_FULL 7
 
@@ -728,6 +728,46 @@ dd_status dd_hash_join_run(const dd_batch_desc *build, const int32_t *build_keys
                            const int32_t *build_proj, int32_t n_build_proj,
                            const int32_t *probe_proj, int32_t n_probe_proj, void *stream,
                            dd_joiner **out);
+/* The outer joins: LEFT, RIGHT and FULL. dd_hash_join_run's parameters, its
+ * keys, layouts, projections and refusals; the five other types are refused here with
+ * DD_ERR_INVALID (they are dd_hash_join_run's), as is a type outside 0..7.
+ *
+ * RIGHT: every inner pair, plus one row per probe row without a match with the build side
+ * NULL. LEFT: every inner pair, plus one row per build row no probe row matched with the
+ * probe side NULL. FULL: both. A NULL-key row is a row without a match.
+ *
+ * The output has TWO SECTIONS of segments. First the probe side's probe_n_segs segments with
+ * its seg_part: rows in probe row order, the matches of one probe row adjacent in an
+ * unspecified order; under RIGHT / FULL a probe row without a match stands there once as
+ * (DD_JOIN_NONE, row), under LEFT it contributes nothing. Then, for LEFT and FULL only, the
+ * build side's build_n_segs segments with its seg_part: segment probe_n_segs + s holds the
+ * unmatched rows of build segment s in build row order as (row, DD_JOIN_NONE) -- where
+ * HashJoinExec emits them, after the partition's probe stream is exhausted. dd_joiner_n_segs
+ * is probe_n_segs (RIGHT) or probe_n_segs + build_n_segs; n_parts is unchanged.
+ *
+ * build_idx and probe_idx are both always present. Every output column of a NULL-extended
+ * side (probe for LEFT, build for RIGHT, both for FULL) has a validity buffer: the source's
+ * byte on a real row (1 if the source has none), 0 on a DD_JOIN_NONE row, whose value bytes
+ * are all zero. Columns of the other side have validity exactly when their source has.
+ * The total over both sections is range-checked after the count pass as above. RIGHT with
+ * an empty probe side and any type with both sides empty succeed with zero rows. */
+
+#define DD_JOIN_NONE 0xffffffffu /* build_idx / probe_idx: this side of the row is absent */
+
+/* seam: HashJoinExec mode=Partitioned, join_type=Left above two NetworkShuffleExec (TPC-H
+ * q13, tests/tpch_plans_test.rs:867); Right / Full in tests/tpcds_plans_test.rs */
+dd_status dd_hash_join_outer_run(const dd_batch_desc *build, const int32_t *build_keys,
+                                 const dd_batch_desc *probe, const int32_t *probe_keys,
+                                 int32_t n_keys, int32_t join_type,
+                                 const int64_t *build_seg_offsets,
+                                 const int32_t *build_seg_part, int32_t build_n_segs,
+                                 int32_t build_n_parts, const int64_t *probe_seg_offsets,
+                                 const int32_t *probe_seg_part, int32_t probe_n_segs,
+                                 int32_t probe_n_parts, const int32_t *build_proj,
+                                 int32_t n_build_proj, const int32_t *probe_proj,
+                                 int32_t n_probe_proj, void *stream, dd_joiner **out);
+/* same seam: output segments: dd_joiner_seg_offsets copies this many + 1 entries */
+int32_t dd_joiner_n_segs(const dd_joiner *j);
 /* same seam: output rows of the HashJoinExec */
 int64_t dd_joiner_n_rows(const dd_joiner *j);
 /* same seam: host_out[n_segs + 1] of the emitting side: output segment s is rows
