@@ -11,9 +11,12 @@ The scan's single-round span is DD_J_SCAN_TILE * DD_J_SUMS_THREADS = 1024 * 1024
 emitting side; test_emitting_side_past_one_scan_round crosses it and checks against a
 vectorised numpy expectation instead of the Python model.
 
-Not run on the GPU: the refusal of an output of 2^31 rows or more. Reaching it means
-billions of chain steps in the count pass; the check itself is one comparison of the exact
-64-bit total on the host."""
+The refusal of an output of 2^31 rows or more is run too, in
+test_refuses_an_output_of_2_31_rows_or_more: one key value on both sides reaches 2^31 and
+2^32 + 4096 pairs with chains of 2048 and 4096 steps per probe lane, and the message must
+name the exact 64-bit total."""
+
+import time
 
 import numpy as np
 import pytest
@@ -459,6 +462,37 @@ def test_refuses_layouts():
                build_layout=ok2, probe_layout=bad)
     with pytest.raises(ValueError, match="one entry more"):
         api.hash_join(a, [0], b, [0], build_layout=lay([0, 8], [0, 1], 2), probe_layout=ok2)
+
+
+# ---------------- the 2^31-row limit ----------------
+
+@pytest.mark.parametrize("nb,npr,total", [(2048, 2**20, 2147483648),
+                                          (4096, 2**20 + 1, 4294971392)])
+def test_refuses_an_output_of_2_31_rows_or_more(main_sides, nb, npr, total):
+    """One i32 key value on both sides, one partition, no projected column: nb * npr pairs.
+    2048 x 2^20 is exactly 2^31, the smallest refused output; 4096 x (2^20 + 1) is
+    2^32 + 4096, which a 32-bit total anywhere between the scan and the host check would
+    read as 4096 rows and accept. Each probe lane walks an nb-step chain inside a next
+    array of 4 * nb bytes, and a wave's lanes walk the same addresses, so the count pass
+    takes milliseconds (the printed wall time). Nothing is emitted. After the
+    refusal the same entry joins the main shape and matches the model."""
+    assert nb * npr == total >= 2**31
+    bb = api.DeviceBatch([col("i32", np.full(nb, 7, dtype=np.int32))])
+    pb = api.DeviceBatch([col("i32", np.full(npr, 7, dtype=np.int32))])
+    try:
+        t0 = time.perf_counter()
+        with pytest.raises(api.DDError) as ei:
+            api.hash_join(bb, [0], pb, [0], "inner", build_proj=[], probe_proj=[])
+        seconds = time.perf_counter() - t0
+    finally:
+        bb.free()
+        pb.free()
+    print(f"inner {nb} x {npr}: refused after {seconds * 1e3:.1f} ms")
+    assert ei.value.status == UNSUPPORTED, str(ei.value)
+    assert f"output of {total} rows is 2^31 or more" in str(ei.value), str(ei.value)
+    build, blay, probe, play = main_sides
+    off, _, _ = check_join(build, [0], probe, [0], "inner", blay, play)
+    assert off[-1] > 1000
 
 
 # ---------------- reuse and what follows the join ----------------

@@ -12,7 +12,10 @@ The count array is cnt[n_probe + n_build] with the build part at index n_probe, 
 test_cnt_seam puts that index off the 4-entry vector, the 1024-entry scan tile and the
 2048-row block; test_past_one_scan_round puts it in the scan's second round.
 
-Not run on the GPU, as in test_gpu_hash_join.py: the refusal of an output of 2^31 rows."""
+The refusal of an output of 2^31 rows or more is run with test_gpu_hash_join.py's shapes,
+for right and for full (one count array over both sections)."""
+
+import time
 
 import numpy as np
 import pytest
@@ -496,6 +499,36 @@ def refuse(status, cause, build, bkeys, probe, pkeys, join_type="full", **kw):
                                        "right_anti"])
 def test_refuses_the_other_join_types(join_type):
     refuse(INVALID, "dd_hash_join_run", fake(["i64"]), [0], fake(["i64"]), [0], join_type)
+
+
+@pytest.mark.parametrize("join_type,nb,npr,total", [("right", 2048, 2**20, 2147483648),
+                                                    ("right", 4096, 2**20 + 1, 4294971392),
+                                                    ("full", 2048, 2**20, 2147483648)])
+def test_refuses_an_output_of_2_31_rows_or_more(main_sides, join_type, nb, npr, total):
+    """test_gpu_hash_join.py's limit shapes through the outer entry: one i32 key value on
+    both sides, one partition, no projected column. 2048 x 2^20 is exactly 2^31 rows;
+    4096 x (2^20 + 1) is 2^32 + 4096, which 32 bits read as 4096. Under "full" the total
+    comes from the one count array that spans both sections: 2^31 from the probe rows, 0
+    from the build rows, every one of which is matched. The printed wall time is the
+    measurement DESIGN.md §20 quotes. After the refusal the same entry joins the main shape
+    and matches the model."""
+    assert nb * npr == total >= 2**31
+    bb = api.DeviceBatch([col("i32", np.full(nb, 7, dtype=np.int32))])
+    pb = api.DeviceBatch([col("i32", np.full(npr, 7, dtype=np.int32))])
+    try:
+        t0 = time.perf_counter()
+        with pytest.raises(api.DDError) as ei:
+            api.outer_join(bb, [0], pb, [0], join_type, build_proj=[], probe_proj=[])
+        seconds = time.perf_counter() - t0
+    finally:
+        bb.free()
+        pb.free()
+    print(f"{join_type} {nb} x {npr}: refused after {seconds * 1e3:.1f} ms")
+    assert ei.value.status == UNSUPPORTED, str(ei.value)
+    assert f"output of {total} rows is 2^31 or more" in str(ei.value), str(ei.value)
+    build, blay, probe, play = main_sides
+    r = check_outer(build, [0], probe, [0], join_type, blay, play)
+    assert r["n_rows"] > 7001
 
 
 def test_refuses_unknown_join_types():
