@@ -136,6 +136,20 @@ def lib():
             fn.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         L.dd_joiner_destroy.restype = None
         L.dd_joiner_destroy.argtypes = [ctypes.c_void_p]
+        L.dd_finalizer_n_cols.restype = ctypes.c_int32
+        L.dd_finalizer_n_cols.argtypes = [ctypes.c_void_p]
+        L.dd_finalizer_col_dtype.restype = ctypes.c_int32
+        L.dd_finalizer_col_dtype.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+        L.dd_sorter_n_rows.restype = ctypes.c_int64
+        L.dd_sorter_n_rows.argtypes = [ctypes.c_void_p]
+        L.dd_sorter_perm.restype = ctypes.c_void_p
+        L.dd_sorter_perm.argtypes = [ctypes.c_void_p]
+        for fn in (L.dd_finalizer_col_data, L.dd_finalizer_col_validity,
+                   L.dd_sorter_col_data, L.dd_sorter_col_validity):
+            fn.restype = ctypes.c_void_p
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+        L.dd_sorter_destroy.restype = None
+        L.dd_sorter_destroy.argtypes = [ctypes.c_void_p]
         L.dd_dict_gc_n_windows.restype = ctypes.c_uint32
         L.dd_dict_gc_indices.restype = ctypes.c_void_p
         L.dd_dict_gc_dict_offsets.restype = ctypes.c_void_p
@@ -1332,3 +1346,251 @@ def outer_join(build: DeviceBatch, build_keys, probe: DeviceBatch, probe_keys, j
     joined = Joined(h, join_type, out_cols, seg_part, bparts)
     assert int(lib().dd_joiner_n_segs(h)) == len(seg_part)
     return joined
+
+
+class Merged:
+    """Output of final_merge_device (dd_finalizer_*): the merged rows kept on the device as
+    typed columns, for a further operator."""
+
+    def __init__(self, h, key_dtypes, ops, n_parts, with_nn):
+        self.h = h
+        self.key_dtypes = list(key_dtypes)
+        self.ops = list(ops)
+        self.n_parts = n_parts
+        self.with_nn = with_nn
+        self.n_groups = int(lib().dd_finalizer_n_groups(h))
+        self.n_cols = int(lib().dd_finalizer_n_cols(h))
+        inv = {v: k for k, v in DTYPE_CODE.items()}
+        self.dtypes = [inv[int(lib().dd_finalizer_col_dtype(h, i))] for i in range(self.n_cols)]
+
+    def group_offsets(self):
+        """Host i64[n_parts + 1]: partition p's groups are rows [off[p], off[p + 1])."""
+        out = np.zeros(self.n_parts + 1, dtype=np.int64)
+        _check(lib().dd_finalizer_group_offsets(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def layout(self):
+        return {"seg_offsets": self.group_offsets(),
+                "seg_part": np.arange(self.n_parts, dtype=np.int32), "n_parts": self.n_parts}
+
+    def batch(self):
+        """(view, layout): a non-owning DeviceBatch over the typed columns (keys, one column
+        per aggregate, then the nn columns if asked for) plus the layout with seg_offsets =
+        group_offsets and identity seg_part, ready for sort_topk, Partitioner, partial_reduce,
+        final_merge or a join. Nothing is copied; this Merged must outlive it."""
+        L = lib()
+        view = [{"dtype": dt, "data_ptr": L.dd_finalizer_col_data(self.h, i),
+                 "valid_ptr": L.dd_finalizer_col_validity(self.h, i)}
+                for i, dt in enumerate(self.dtypes)]
+        return DeviceBatch.from_device(view, self.n_groups), self.layout()
+
+    def col(self, i):
+        """Host copy of column i in Partitioner.col_out's shape (tests)."""
+        dt, n = self.dtypes[i], self.n_groups
+        res = {"dtype": dt, "data": fixed_out(dt, np.zeros(0, dtype=FIXED_NP[dt]))}
+        if n:
+            res["data"] = fixed_out(dt, _d2h(lib().dd_finalizer_col_data(self.h, i),
+                                             n * ELEM_SIZE[dt], FIXED_NP[dt]))
+        vp = lib().dd_finalizer_col_validity(self.h, i)
+        has_valid = i < len(self.key_dtypes) + len(self.ops) and not (
+            i >= len(self.key_dtypes) and self.ops[i - len(self.key_dtypes)] == "count")
+        if has_valid:
+            res["valid"] = _d2h(vp, n, np.uint8) if n else np.zeros(0, dtype=np.uint8)
+        return res
+
+    def fetch(self):
+        """The dict final_merge returns for the same input (host copies of the interleaved
+        state), so a test can hold the columns to it."""
+        n, nk, na = self.n_groups, len(self.key_dtypes), len(self.ops)
+        keys = np.zeros((n, nk), dtype=np.uint64)
+        keynull = np.zeros(n, dtype=np.uint32)
+        vals = np.zeros((n, na), dtype=np.float64)
+        nn = np.zeros((n, na), dtype=np.uint64)
+        hi = np.zeros((n, na), dtype=np.uint64)
+        ms = (ctypes.c_float * 3)()
+        _check(lib().dd_finalizer_kernel_ms(self.h, ms))
+        if n:
+            _check(lib().dd_finalizer_fetch(
+                self.h, keys.ctypes.data_as(ctypes.c_void_p),
+                keynull.ctypes.data_as(ctypes.c_void_p), vals.ctypes.data_as(ctypes.c_void_p)))
+            _check(lib().dd_finalizer_fetch_nn(self.h, nn.ctypes.data_as(ctypes.c_void_p)))
+            _check(lib().dd_finalizer_fetch_hi(self.h, hi.ctypes.data_as(ctypes.c_void_p)))
+        return {"keys": keys, "keynull": keynull, "aggs": vals, "aggs_hi": hi, "nn": nn,
+                "group_offsets": self.group_offsets(), "kernel_ms": list(ms)}
+
+    def destroy(self):
+        if self.h:
+            lib().dd_finalizer_destroy(self.h)
+            self.h = None
+
+
+def final_merge_device(batch: DeviceBatch, key_idx, aggs, seg_offsets=None, seg_part=None,
+                       n_parts=1, with_nn=False):
+    """final_merge that keeps its result on the device: the same arguments,
+    kernels and refusals (dd_final_merge_run), then dd_finalizer_columns turns the interleaved
+    state into typed device columns. Returns a Merged.
+
+    Columns: each key in its input dtype with validity from keynull (a float key comes out
+    canonicalised, +0.0 for -0.0 and one quiet NaN, because the group identity is); one
+    column per aggregate, i64 for count / sum_i64 / min_i64 / max_i64, f64 for sum_f64 /
+    min_f64 / max_f64, dec128 for sum_dec128, with validity nn != 0 (a total nn of 0 is SQL
+    NULL; count has no validity buffer and is never NULL); with_nn adds one i64 nn column per
+    aggregate after the value columns."""
+    nk = len(key_idx)
+    na = len(aggs)
+    if seg_offsets is None:
+        seg_offsets, seg_part, n_parts = [0, batch.n_rows], [0], 1
+    off = np.ascontiguousarray(seg_offsets, dtype=np.int64)
+    part = np.ascontiguousarray(seg_part, dtype=np.int32)
+    if len(off) != len(part) + 1:
+        raise ValueError("final_merge_device: seg_offsets must have one entry more than "
+                         "seg_part")
+    keysc = (ctypes.c_int32 * max(nk, 1))(*key_idx)
+    statec = (ctypes.c_int32 * max(na, 1))(*[c for c, _, _ in aggs])
+    opsc = (ctypes.c_int32 * max(na, 1))(*[AGG_OPS[o] for _, o, _ in aggs])
+    nnc = (ctypes.c_int32 * max(na, 1))(*[-1 if c is None else c for _, _, c in aggs])
+    h = ctypes.c_void_p()
+    _check(lib().dd_final_merge_run(
+        ctypes.byref(batch.desc), keysc, nk, statec, opsc, nnc, na,
+        off.ctypes.data_as(ctypes.c_void_p), part.ctypes.data_as(ctypes.c_void_p),
+        ctypes.c_int32(len(part)), ctypes.c_int32(n_parts), None, ctypes.byref(h)))
+    try:
+        key_dtypes = [batch.cols[k]["dtype"] for k in key_idx]
+        kdt = (ctypes.c_int32 * max(nk, 1))(*[DTYPE_CODE[d] for d in key_dtypes])
+        _check(lib().dd_finalizer_columns(h, kdt, ctypes.c_int32(nk), opsc,
+                                          ctypes.c_int32(na), ctypes.c_int32(int(with_nn)),
+                                          None))
+    except Exception:
+        lib().dd_finalizer_destroy(h)
+        raise
+    return Merged(h, key_dtypes, [o for _, o, _ in aggs], int(n_parts), bool(with_nn))
+
+
+SORT_DESC = 1         # DD_SORT_DESC
+SORT_NULLS_FIRST = 2  # DD_SORT_NULLS_FIRST
+
+
+class Sorted:
+    """Output of sort_topk (dd_sorter_*): perm, the gathered columns and the new segment
+    offsets, all on the device; one segment per partition."""
+
+    def __init__(self, h, out_cols, n_parts):
+        self.h = h
+        self._out_cols = out_cols  # (dtype, source has validity) per projected column
+        self._n_parts = n_parts
+        self.n_rows = int(lib().dd_sorter_n_rows(h))
+
+    def seg_offsets(self):
+        """Host i64[n_parts + 1]: partition p's rows are [off[p], off[p + 1])."""
+        out = np.zeros(self._n_parts + 1, dtype=np.int64)
+        _check(lib().dd_sorter_seg_offsets(self.h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def layout(self):
+        return {"seg_offsets": self.seg_offsets(),
+                "seg_part": np.arange(self._n_parts, dtype=np.int32), "n_parts": self._n_parts}
+
+    def perm_ptr(self):
+        """Device pointer to u32[n_rows], the input row of each output row (None at zero
+        rows)."""
+        return lib().dd_sorter_perm(self.h)
+
+    def perm(self):
+        """perm as a host u32[n_rows] copy (tests)."""
+        if not self.n_rows:
+            return np.zeros(0, dtype=np.uint32)
+        return _d2h(self.perm_ptr(), self.n_rows * 4, np.uint32)
+
+    def batch(self):
+        """(view, layout): a non-owning DeviceBatch over the projected columns plus
+        {"seg_offsets", "seg_part", "n_parts"}, ready for Partitioner, partial_reduce,
+        final_merge, a join or another sort_topk. Nothing is copied; this Sorted must outlive
+        it."""
+        if not self._out_cols:
+            raise ValueError("sort_topk: no projected columns, so there is no batch (perm only)")
+        L = lib()
+        view = [{"dtype": dt, "data_ptr": L.dd_sorter_col_data(self.h, i),
+                 "valid_ptr": L.dd_sorter_col_validity(self.h, i)}
+                for i, (dt, _) in enumerate(self._out_cols)]
+        return DeviceBatch.from_device(view, self.n_rows), self.layout()
+
+    def col(self, i):
+        """Host copy of projected column i in Partitioner.col_out's shape (tests)."""
+        dt, has_valid = self._out_cols[i]
+        n = self.n_rows
+        res = {"dtype": dt, "data": fixed_out(dt, np.zeros(0, dtype=FIXED_NP[dt]))}
+        if n:
+            res["data"] = fixed_out(dt, _d2h(lib().dd_sorter_col_data(self.h, i),
+                                             n * ELEM_SIZE[dt], FIXED_NP[dt]))
+        if has_valid:
+            res["valid"] = (_d2h(lib().dd_sorter_col_validity(self.h, i), n, np.uint8) if n
+                            else np.zeros(0, dtype=np.uint8))
+        return res
+
+    def info(self):
+        """{"passes_planned": radix passes the key dtypes and the layout call for,
+        "passes_run": those left after the census dropped every constant digit (all of them
+        under DD_SORT_SKIP=0), "tile_rows": rows per scatter tile, "words": 64-bit words per
+        row}. Zero passes when the result is empty (no device work)."""
+        out = (ctypes.c_int32 * 4)()
+        _check(lib().dd_sorter_info(self.h, out))
+        return dict(zip(("passes_planned", "passes_run", "tile_rows", "words"),
+                        (int(v) for v in out)))
+
+    def kernel_ms(self):
+        """[encode + census, passes, segment output, gather] hipEvent times in ms."""
+        out = (ctypes.c_float * 4)()
+        _check(lib().dd_sorter_kernel_ms(self.h, out))
+        return list(out)
+
+    def destroy(self):
+        if self.h:
+            lib().dd_sorter_destroy(self.h)
+            self.h = None
+
+
+def sort_topk(batch: DeviceBatch, keys, layout=None, fetch=None, proj=None):
+    """GPU SortExec / TopK per partition above the shuffle (dd_sort_run; DESIGN.md §22;
+    sortref.sort_ref is the same rules in numpy).
+
+    keys: 1..4 of (col, descending, nulls_first), the two flags independent (DataFusion
+    prints `x DESC` for DESC NULLS FIRST and `x ASC NULLS LAST` for the other default);
+    dtypes u8, bool, i16, i32, i64, f32, f64 (totalOrder on the raw bits), dec128.
+    layout: {"seg_offsets", "seg_part", "n_parts"} as exchanged_batch, partitioned_batch,
+    Joined.batch, Merged.batch and Sorted.batch return it; default one segment, one partition.
+    fetch: None keeps every row, k >= 0 the first min(k, rows) of each partition.
+    proj: columns to gather on the device, default all; fixed-width dtypes only.
+    Returns a Sorted: one segment per partition, rows in key order, ties in input order
+    (stable). sort_topk over Sorted.batch() with sortref.collapsed_layout and the same fetch
+    is the SortPreservingMergeExec(fetch) at the top of the plan."""
+    try:
+        keys = [(int(c), bool(d), bool(nf)) for c, d, nf in keys]
+    except (TypeError, ValueError):
+        raise ValueError("sort_topk: keys are (col, descending, nulls_first) triples") from None
+    if fetch is not None and int(fetch) != fetch:
+        raise ValueError("sort_topk: fetch must be None or an integer")
+    if proj is None:
+        proj = list(range(batch.desc.n_cols))
+    proj = [int(c) for c in proj]
+    if layout is None:
+        layout = {"seg_offsets": [0, batch.n_rows], "seg_part": [0], "n_parts": 1}
+    off = np.ascontiguousarray(layout["seg_offsets"], dtype=np.int64)
+    part = np.ascontiguousarray(layout["seg_part"], dtype=np.int32)
+    n_parts = int(layout["n_parts"])
+    if len(off) != len(part) + 1:
+        raise ValueError("sort_topk: seg_offsets must have one entry more than seg_part")
+    # None is the library's -1; a negative fetch reaches it as one it refuses
+    fetch_c = -1 if fetch is None else int(fetch) if fetch >= 0 else min(int(fetch), -2)
+    nk = len(keys)
+    kc = (ctypes.c_int32 * max(nk, 1))(*[c for c, _, _ in keys])
+    kf = (ctypes.c_int32 * max(nk, 1))(*[(SORT_DESC if d else 0) | (SORT_NULLS_FIRST if nf else 0)
+                                         for _, d, nf in keys])
+    pc = (ctypes.c_int32 * max(len(proj), 1))(*proj)
+    h = ctypes.c_void_p()
+    _check(lib().dd_sort_run(
+        ctypes.byref(batch.desc), kc, kf, ctypes.c_int32(nk), pc, ctypes.c_int32(len(proj)),
+        off.ctypes.data_as(ctypes.c_void_p), part.ctypes.data_as(ctypes.c_void_p),
+        ctypes.c_int32(len(part)), ctypes.c_int32(n_parts),
+        ctypes.c_int64(fetch_c), None, ctypes.byref(h)))
+    out_cols = [(batch.cols[i]["dtype"], bool(batch.desc.cols[i].validity)) for i in proj]
+    return Sorted(h, out_cols, n_parts)

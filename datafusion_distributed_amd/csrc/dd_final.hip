@@ -394,3 +394,52 @@ extern "C" hipError_t dd_launch_final_merge(const dd_kargs *a, const dd_final_pl
                            out_aggs, out_nn);
     return hipGetLastError();
 }
+
+/* ---------------- typed device columns for a further operator ----------
+ * The interleaved state of a finished merge, one thread per group, as columns: each key in its
+ * input dtype from the canonical key bits (a float key therefore comes out canonicalised: +0.0
+ * for -0.0, one quiet NaN) with validity from keynull; one column per aggregate (i64, f64, or
+ * dec128 from (lo, hi)) with validity nn != 0; optionally nn itself as i64. */
+__global__ __launch_bounds__(F_THREADS) void k_final_columns(
+    dd_final_cols c, int64_t n_groups, const uint64_t *keys, const uint32_t *keynull,
+    const uint64_t *aggs, const uint64_t *hi, const uint64_t *nn) {
+    const int64_t g = (int64_t)blockIdx.x * F_THREADS + threadIdx.x;
+    if (g >= n_groups) return;
+    const int nk = c.n_keys, na = c.n_aggs;
+    const uint32_t knull = keynull[g];
+#pragma unroll
+    for (int k = 0; k < F_MAXK; k++) {
+        if (k >= nk) break;
+        const uint64_t b = keys[(size_t)g * nk + k];
+        switch (c.key_dtype[k]) { /* wave-uniform */
+        case DD_KDT_U8:
+        case DD_KDT_BOOL: ((uint8_t *)c.key_data[k])[g] = (uint8_t)b; break;
+        case DD_KDT_I16: ((uint16_t *)c.key_data[k])[g] = (uint16_t)b; break;
+        case DD_KDT_I32:
+        case DD_KDT_F32: ((uint32_t *)c.key_data[k])[g] = (uint32_t)b; break;
+        default: ((uint64_t *)c.key_data[k])[g] = b; /* i64, f64 */
+        }
+        c.key_valid[k][g] = (uint8_t)(((knull >> k) & 1u) == 0);
+    }
+#pragma unroll
+    for (int j = 0; j < F_MAXA; j++) {
+        if (j >= na) break;
+        const uint64_t lo = aggs[(size_t)g * na + j], cnt = nn[(size_t)g * na + j];
+        if (c.ops[j] == DD_AGG_SUM_DEC128)
+            ((dd_u128 *)c.agg_data[j])[g] = dd_u128{lo, hi[(size_t)g * na + j]};
+        else
+            ((uint64_t *)c.agg_data[j])[g] = lo;
+        if (c.agg_valid[j]) c.agg_valid[j][g] = (uint8_t)(cnt != 0);
+        if (c.nn_data[j]) c.nn_data[j][g] = (int64_t)cnt;
+    }
+}
+
+extern "C" hipError_t dd_launch_final_columns(const dd_final_cols *c, int64_t n_groups,
+                                              const uint64_t *keys, const uint32_t *keynull,
+                                              const uint64_t *aggs, const uint64_t *hi,
+                                              const uint64_t *nn, hipStream_t s) {
+    if (n_groups == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_final_columns, dim3((unsigned)((n_groups + F_THREADS - 1) / F_THREADS)),
+                       dim3(F_THREADS), 0, s, *c, n_groups, keys, keynull, aggs, hi, nn);
+    return hipGetLastError();
+}

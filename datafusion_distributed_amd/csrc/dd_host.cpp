@@ -2480,12 +2480,24 @@ struct dd_finalizer {
     uint64_t *hi = nullptr;
     uint64_t *nn = nullptr;
     float kernel_ms[3] = {0, 0, 0}; /* claim, scan, merge */
+    /* dd_finalizer_columns: keys, aggregates, then the optional nn columns */
+    std::vector<int32_t> col_dtype;
+    std::vector<void *> col_data;
+    std::vector<uint8_t *> col_validity; /* null: the column has none */
+    void free_columns() {
+        for (void *p : col_data) (void)hipFree(p);
+        for (uint8_t *p : col_validity) (void)hipFree(p);
+        col_dtype.clear();
+        col_data.clear();
+        col_validity.clear();
+    }
     ~dd_finalizer() {
         (void)hipFree(keys);
         (void)hipFree(keynull);
         (void)hipFree(aggs);
         (void)hipFree(hi);
         (void)hipFree(nn);
+        free_columns();
     }
 };
 
@@ -2751,6 +2763,92 @@ extern "C" dd_status dd_finalizer_kernel_ms(const dd_finalizer *f, float *out3) 
     if (!f || !out3) return set_err(DD_ERR_INVALID, "null argument");
     memcpy(out3, f->kernel_ms, sizeof(f->kernel_ms));
     return DD_OK;
+}
+
+/* The merged rows as typed device columns (k_final_columns): n_keys key
+ * columns, n_aggs aggregate columns, then n_aggs i64 nn columns when with_nn. The finalizer
+ * keeps no plan, so the key dtypes and the ops of the run are passed again. */
+extern "C" dd_status dd_finalizer_columns(dd_finalizer *f, const int32_t *key_dtypes,
+                                          int32_t n_keys, const int32_t *agg_ops,
+                                          int32_t n_aggs, int32_t with_nn, void *stream) {
+    if (!f || !key_dtypes || !agg_ops) return set_err(DD_ERR_INVALID, "null argument");
+    if (n_keys != f->n_keys || n_aggs != f->n_aggs)
+        return set_err(DD_ERR_INVALID, "final columns: key / aggregate count differs from "
+                                       "the merge's");
+    dd_final_cols c;
+    memset(&c, 0, sizeof(c));
+    c.n_keys = n_keys;
+    c.n_aggs = n_aggs;
+    for (int k = 0; k < n_keys; k++) {
+        switch (key_dtypes[k]) {
+        case DD_DT_U8: case DD_DT_BOOL: case DD_DT_I16: case DD_DT_I32: case DD_DT_I64:
+        case DD_DT_F32: case DD_DT_F64:
+            break;
+        default:
+            return set_err(DD_ERR_INVALID, "final columns: not a final merge key dtype");
+        }
+        c.key_dtype[k] = key_dtypes[k];
+    }
+    for (int j = 0; j < n_aggs; j++) {
+        if (agg_ops[j] < 0 || agg_ops[j] > DD_AGG_SUM_DEC128)
+            return set_err(DD_ERR_INVALID, "final columns: unknown aggregate op");
+        c.ops[j] = agg_ops[j];
+    }
+    f->free_columns();
+    const int64_t ng = f->n_groups;
+    const int n_cols = n_keys + n_aggs * (with_nn ? 2 : 1);
+    f->col_dtype.assign((size_t)n_cols, 0);
+    f->col_data.assign((size_t)n_cols, nullptr);
+    f->col_validity.assign((size_t)n_cols, nullptr);
+    for (int i = 0; i < n_cols; i++) {
+        int dt = DD_DT_I64; /* count, the i64 aggregates, nn */
+        bool has_valid = true;
+        if (i < n_keys) {
+            dt = key_dtypes[i];
+        } else if (i < n_keys + n_aggs) {
+            const int op = agg_ops[i - n_keys];
+            if (op == DD_AGG_SUM_DEC128) dt = DD_DT_DEC128;
+            else if (op == DD_AGG_SUM_F64 || op == DD_AGG_MIN_F64 || op == DD_AGG_MAX_F64)
+                dt = DD_DT_F64;
+            has_valid = op != DD_AGG_COUNT;
+        } else {
+            has_valid = false;
+        }
+        f->col_dtype[i] = dt;
+        if (ng == 0) continue; /* no device work, as the run itself at zero rows */
+        HIP_TRY(hipMalloc(&f->col_data[i], (size_t)ng * fixed_elem_size(dt)));
+        if (has_valid) HIP_TRY(hipMalloc((void **)&f->col_validity[i], (size_t)ng));
+        if (i < n_keys) {
+            c.key_data[i] = f->col_data[i];
+            c.key_valid[i] = f->col_validity[i];
+        } else if (i < n_keys + n_aggs) {
+            c.agg_data[i - n_keys] = f->col_data[i];
+            c.agg_valid[i - n_keys] = f->col_validity[i];
+        } else {
+            c.nn_data[i - n_keys - n_aggs] = (int64_t *)f->col_data[i];
+        }
+    }
+    if (ng == 0) return DD_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(dd_launch_final_columns(&c, ng, f->keys, f->keynull, f->aggs, f->hi, f->nn, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DD_OK;
+}
+
+extern "C" int32_t dd_finalizer_n_cols(const dd_finalizer *f) {
+    return f ? (int32_t)f->col_data.size() : 0;
+}
+
+extern "C" int32_t dd_finalizer_col_dtype(const dd_finalizer *f, int32_t i) {
+    return f && i >= 0 && i < (int32_t)f->col_dtype.size() ? f->col_dtype[i] : 0;
+}
+
+extern "C" const void *dd_finalizer_col_data(const dd_finalizer *f, int32_t i) {
+    return f && i >= 0 && i < (int32_t)f->col_data.size() ? f->col_data[i] : nullptr;
+}
+
+extern "C" const uint8_t *dd_finalizer_col_validity(const dd_finalizer *f, int32_t i) {
+    return f && i >= 0 && i < (int32_t)f->col_validity.size() ? f->col_validity[i] : nullptr;
 }
 
 extern "C" void dd_finalizer_destroy(dd_finalizer *f) { delete f; }
@@ -3317,6 +3415,307 @@ extern "C" dd_status dd_joiner_kernel_ms(const dd_joiner *j, float *out5) {
 }
 
 extern "C" void dd_joiner_destroy(dd_joiner *j) { delete j; }
+
+/* ---------------- sort / top-k above the shuffle (dd_sorter) -------------- */
+
+struct dd_sorter {
+    int64_t n_rows = 0;               /* output rows, after fetch */
+    std::vector<int64_t> seg_offsets; /* [n_parts + 1] */
+    uint32_t *perm = nullptr;         /* source row of each output row */
+    std::vector<void *> col_data;     /* per projected column; null only at zero rows */
+    std::vector<uint8_t *> col_validity; /* null when the source has none */
+    int32_t info[4] = {0, 0, DD_S_TILE, 0}; /* passes planned, passes run, tile rows, words */
+    float kernel_ms[4] = {0, 0, 0, 0};      /* encode + census, passes, seg out, gather */
+    ~dd_sorter() {
+        (void)hipFree(perm);
+        for (void *p : col_data) (void)hipFree(p);
+        for (uint8_t *p : col_validity) (void)hipFree(p);
+    }
+};
+
+extern "C" dd_status dd_sort_run(const dd_batch_desc *batch, const int32_t *key_cols,
+                                 const int32_t *key_flags, int32_t n_keys,
+                                 const int32_t *proj_cols, int32_t n_proj,
+                                 const int64_t *seg_offsets, const int32_t *seg_part,
+                                 int32_t n_segs, int32_t n_parts, int64_t fetch, void *stream,
+                                 dd_sorter **out) {
+    if (!batch || !key_cols || !key_flags || !seg_offsets || !seg_part || !out)
+        return set_err(DD_ERR_INVALID, "sort: null argument");
+    if (n_keys < 1 || n_keys > DD_S_MAX_KEYS)
+        return set_err(DD_ERR_INVALID, "sort: 1..4 sort keys");
+    if (fetch < -1) return set_err(DD_ERR_INVALID, "sort: fetch must be -1 (all rows) or >= 0");
+    const int64_t n = batch->n_rows;
+    if (n < 0 || n >= ((int64_t)1 << 31))
+        return set_err(DD_ERR_INVALID, "sort: n_rows must be below 2^31 (perm holds 32-bit row "
+                                       "ids)");
+    if (batch->n_cols < 1 || batch->n_cols > DD_MAX_COLS)
+        return set_err(DD_ERR_INVALID, "sort: column count out of range");
+    for (int k = 0; k < n_keys; k++) {
+        if (key_cols[k] < 0 || key_cols[k] >= batch->n_cols)
+            return set_err(DD_ERR_INVALID, "sort: key column index out of range");
+        if (key_flags[k] & ~(DD_SORT_DESC | DD_SORT_NULLS_FIRST))
+            return set_err(DD_ERR_INVALID, "sort: unknown key flag bits");
+        const dd_col_desc &cd = batch->cols[key_cols[k]];
+        switch (cd.dtype) {
+        case DD_DT_DICT32:
+            return set_err(DD_ERR_UNSUPPORTED,
+                           "sort: dict32 keys are not supported: dictionary index order is "
+                           "not value order");
+        case DD_DT_UTF8:
+            return set_err(DD_ERR_UNSUPPORTED, "sort: utf8 / utf8view keys are not supported");
+        case DD_DT_DEC128:
+            if ((uintptr_t)cd.data % 16)
+                return set_err(DD_ERR_INVALID, "sort: dec128 key data must be 16-byte aligned");
+            break;
+        case DD_DT_U8: case DD_DT_BOOL: case DD_DT_I16: case DD_DT_I32: case DD_DT_I64:
+        case DD_DT_F32: case DD_DT_F64:
+            break;
+        default:
+            return set_err(DD_ERR_INVALID, "sort: unknown key dtype");
+        }
+    }
+    if (n_proj < 0 || n_proj > DD_MAX_COLS || (n_proj > 0 && !proj_cols))
+        return set_err(DD_ERR_INVALID, "sort: projection list out of range");
+    for (int i = 0; i < n_proj; i++) {
+        if (proj_cols[i] < 0 || proj_cols[i] >= batch->n_cols)
+            return set_err(DD_ERR_INVALID, "sort: projected column index out of range");
+        const dd_col_desc &cd = batch->cols[proj_cols[i]];
+        if (cd.dtype == DD_DT_UTF8)
+            return set_err(DD_ERR_UNSUPPORTED, "sort: projection: a var-width (utf8 / "
+                                               "utf8view) column is not supported");
+        if (cd.dtype == DD_DT_DICT32)
+            return set_err(DD_ERR_UNSUPPORTED,
+                           "sort: projection: a dict32 column is not supported");
+        if (fixed_elem_size(cd.dtype) == 0)
+            return set_err(DD_ERR_INVALID, "sort: projection: unknown dtype");
+        if (cd.dtype == DD_DT_DEC128 && (uintptr_t)cd.data % 16)
+            return set_err(DD_ERR_INVALID, "sort: dec128 column data must be 16-byte aligned");
+    }
+    /* the layout, by dd_final_merge_run's checks */
+    if (n_segs < 1 || n_parts < 1)
+        return set_err(DD_ERR_INVALID, "sort: malformed segment layout: at least one segment "
+                                       "and one partition");
+    if (seg_offsets[0] != 0 || seg_offsets[n_segs] != n)
+        return set_err(DD_ERR_INVALID, "sort: malformed segment layout: seg_offsets must run "
+                                       "from 0 to n_rows");
+    std::vector<int64_t> in_off((size_t)n_parts + 1, 0), out_off((size_t)n_parts + 1, 0);
+    for (int s = 0; s < n_segs; s++) {
+        if (seg_offsets[s + 1] < seg_offsets[s])
+            return set_err(DD_ERR_INVALID, "sort: malformed segment layout: seg_offsets "
+                                           "decrease");
+        if (seg_part[s] < 0 || seg_part[s] >= n_parts)
+            return set_err(DD_ERR_INVALID, "sort: malformed segment layout: seg_part outside "
+                                           "[0, n_parts)");
+        in_off[(size_t)seg_part[s] + 1] += seg_offsets[s + 1] - seg_offsets[s];
+    }
+    /* rows per partition -> where each partition starts in the sorted order, and in the
+     * output once fetch has cut it */
+    for (int p = 0; p < n_parts; p++) {
+        const int64_t rows = in_off[(size_t)p + 1];
+        out_off[(size_t)p + 1] = out_off[p] + (fetch >= 0 && fetch < rows ? fetch : rows);
+        in_off[(size_t)p + 1] += in_off[p];
+    }
+    const int64_t n_out = out_off[n_parts];
+
+    dd_sort_keys sk;
+    memset(&sk, 0, sizeof(sk));
+    sk.n_keys = n_keys;
+    int word_of[DD_S_MAX_KEYS];
+    int nw = 0;
+    for (int k = 0; k < n_keys; k++) {
+        const dd_col_desc &cd = batch->cols[key_cols[k]];
+        sk.dtype[k] = cd.dtype;
+        sk.flags[k] = key_flags[k];
+        sk.data[k] = cd.data;
+        sk.valid[k] = (const uint8_t *)cd.validity;
+        word_of[k] = nw;
+        sk.wkey[nw] = k;
+        sk.wpart[nw++] = 0;
+        if (cd.dtype == DD_DT_DEC128) {
+            sk.wkey[nw] = k;
+            sk.wpart[nw++] = 1;
+        }
+    }
+    const int meta = nw;
+    sk.wkey[meta] = -1;
+    sk.n_words = nw + 1;
+
+    auto so = std::unique_ptr<dd_sorter>(new dd_sorter());
+    so->n_rows = n_out;
+    so->seg_offsets = out_off;
+    so->col_data.assign((size_t)n_proj, nullptr);
+    so->col_validity.assign((size_t)n_proj, nullptr);
+    so->info[3] = sk.n_words;
+    if (n_out == 0) { /* no rows, or fetch = 0: empty segments, no device work */
+        *out = so.release();
+        return DD_OK;
+    }
+    if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
+
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n_tiles = (size_t)((n + DD_S_TILE - 1) / DD_S_TILE);
+    const size_t n_h = n_tiles * 256;
+    const size_t nb = (n_h + DD_S_SCAN_TILE - 1) / DD_S_SCAN_TILE;
+    const size_t census_n = (size_t)sk.n_words * 8 * 256;
+    dd_dev_scratch ws;
+    int64_t *d_seg_off = nullptr, *d_in_off = nullptr, *d_out_off = nullptr;
+    int32_t *d_seg_part = nullptr;
+    uint64_t *words = nullptr, *wbuf[2] = {nullptr, nullptr};
+    uint32_t *pbuf[2] = {nullptr, nullptr}, *census = nullptr, *hist = nullptr, *sums = nullptr;
+    if (!ws.alloc(&d_seg_off, ((size_t)n_segs + 1) * 8) ||
+        !ws.alloc(&d_seg_part, (size_t)n_segs * 4) ||
+        !ws.alloc(&d_in_off, ((size_t)n_parts + 1) * 8) ||
+        !ws.alloc(&d_out_off, ((size_t)n_parts + 1) * 8) ||
+        !ws.alloc(&words, (size_t)sk.n_words * (size_t)n * 8) ||
+        !ws.alloc(&wbuf[0], (size_t)n * 8) || !ws.alloc(&wbuf[1], (size_t)n * 8) ||
+        !ws.alloc(&pbuf[0], (size_t)n * 4) || !ws.alloc(&pbuf[1], (size_t)n * 4) ||
+        !ws.alloc(&census, census_n * 4) || !ws.alloc(&hist, n_h * 4) ||
+        !ws.alloc(&sums, (nb + 1) * 4))
+        return set_err(DD_ERR_HIP, "sort: workspace alloc");
+    hipEvent_t ev[6] = {};
+    struct ev_guard {
+        hipEvent_t *e;
+        ~ev_guard() {
+            for (int i = 0; i < 6; i++)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } evg{ev};
+    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemcpyAsync(d_seg_off, seg_offsets, ((size_t)n_segs + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_seg_part, seg_part, (size_t)n_segs * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_in_off, in_off.data(), ((size_t)n_parts + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_out_off, out_off.data(), ((size_t)n_parts + 1) * 8,
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s)); /* pageable host sources: the copies have left them */
+
+    HIP_TRY(hipEventRecord(ev[0], s));
+    HIP_TRY(hipMemsetAsync(census, 0, census_n * 4, s));
+    HIP_TRY(dd_launch_sort_encode(&sk, n, d_seg_off, d_seg_part, n_segs, words, pbuf[0], census,
+                                  s));
+    HIP_TRY(hipEventRecord(ev[1], s));
+    /* the run's one mid-run synchronisation: the census decides which passes run */
+    std::vector<uint32_t> census_h(census_n);
+    HIP_TRY(hipMemcpyAsync(census_h.data(), census, census_n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+
+    /* DD_SORT_SKIP=0: run every planned pass (A/B and tests); read per call */
+    const char *skip_env = getenv("DD_SORT_SKIP");
+    const bool skip = !(skip_env && atoi(skip_env) == 0);
+    struct dd_sort_pass {
+        int word, shift;
+    };
+    std::vector<dd_sort_pass> passes;
+    int planned = 0;
+    /* byte j of word w: dropped when one bin holds every row */
+    auto consider = [&](int w, int j) {
+        planned++;
+        const uint32_t *h = census_h.data() + ((size_t)w * 8 + j) * 256;
+        bool constant = false;
+        for (int b = 0; b < 256; b++) constant = constant || h[b] == (uint32_t)n;
+        if (!skip || !constant) passes.push_back({w, 8 * j});
+    };
+    /* least significant first: the last key's low digit ... the first key's null rank, then
+     * the partition id */
+    for (int k = n_keys - 1; k >= 0; k--) {
+        if (sk.dtype[k] == DD_DT_DEC128) {
+            for (int j = 0; j < 8; j++) consider(word_of[k] + 1, j);
+            for (int j = 0; j < 8; j++) consider(word_of[k], j);
+        } else {
+            const int nd = fixed_elem_size(sk.dtype[k]);
+            for (int j = 0; j < nd; j++) consider(word_of[k], j);
+        }
+        if (sk.valid[k]) consider(meta, k);
+    }
+    int pbits = 0;
+    while (((int64_t)1 << pbits) < n_parts) pbits++;
+    for (int j = 0; j < (pbits + 7) / 8; j++) consider(meta, 4 + j);
+    so->info[0] = planned;
+    so->info[1] = (int32_t)passes.size();
+
+    HIP_TRY(hipEventRecord(ev[2], s));
+    int wi = -1, pi = 0, cur_word = -1; /* wbuf / pbuf holding the current word and perm */
+    for (const dd_sort_pass &ps : passes) {
+        const uint64_t *src = words + (size_t)ps.word * (size_t)n;
+        const uint64_t *win;
+        if (ps.word == cur_word) {
+            win = wbuf[wi];
+        } else if (cur_word < 0) { /* perm is still the identity: the word array as it is */
+            win = src;
+        } else {
+            HIP_TRY(dd_launch_sort_gather_word(src, pbuf[pi], n, wbuf[0], s));
+            wi = 0;
+            win = wbuf[0];
+        }
+        cur_word = ps.word;
+        const int wo = wi < 0 ? 0 : 1 - wi;
+        HIP_TRY(dd_launch_sort_pass(win, pbuf[pi], n, ps.shift, hist, sums, wbuf[wo],
+                                    pbuf[1 - pi], s));
+        wi = wo;
+        pi = 1 - pi;
+    }
+    HIP_TRY(hipEventRecord(ev[3], s));
+    HIP_TRY(hipMalloc((void **)&so->perm, (size_t)n_out * 4));
+    HIP_TRY(dd_launch_sort_seg_out(pbuf[pi], d_in_off, d_out_off, n_parts, n_out, so->perm, s));
+    HIP_TRY(hipEventRecord(ev[4], s));
+    dd_join_gather g;
+    memset(&g, 0, sizeof(g));
+    for (int i = 0; i < n_proj; i++) {
+        const dd_col_desc &cd = batch->cols[proj_cols[i]];
+        const int c = g.n_cols++;
+        g.elem[c] = fixed_elem_size(cd.dtype);
+        g.src[c] = cd.data;
+        g.src_valid[c] = (const uint8_t *)cd.validity;
+        HIP_TRY(hipMalloc(&so->col_data[i], (size_t)n_out * g.elem[c]));
+        g.dst[c] = so->col_data[i];
+        if (cd.validity) {
+            HIP_TRY(hipMalloc((void **)&so->col_validity[i], (size_t)n_out));
+            g.dst_valid[c] = so->col_validity[i];
+        }
+    }
+    HIP_TRY(dd_launch_join_gather(&g, so->perm, n_out, s));
+    HIP_TRY(hipEventRecord(ev[5], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    (void)hipEventElapsedTime(&so->kernel_ms[0], ev[0], ev[1]);
+    (void)hipEventElapsedTime(&so->kernel_ms[1], ev[2], ev[3]);
+    (void)hipEventElapsedTime(&so->kernel_ms[2], ev[3], ev[4]);
+    (void)hipEventElapsedTime(&so->kernel_ms[3], ev[4], ev[5]);
+    *out = so.release();
+    return DD_OK;
+}
+
+extern "C" int64_t dd_sorter_n_rows(const dd_sorter *so) { return so ? so->n_rows : 0; }
+
+extern "C" dd_status dd_sorter_seg_offsets(const dd_sorter *so, int64_t *host_out) {
+    if (!so || !host_out) return set_err(DD_ERR_INVALID, "null argument");
+    memcpy(host_out, so->seg_offsets.data(), so->seg_offsets.size() * 8);
+    return DD_OK;
+}
+
+extern "C" const uint32_t *dd_sorter_perm(const dd_sorter *so) { return so->perm; }
+
+extern "C" const void *dd_sorter_col_data(const dd_sorter *so, int32_t i) {
+    return i >= 0 && i < (int32_t)so->col_data.size() ? so->col_data[i] : nullptr;
+}
+
+extern "C" const uint8_t *dd_sorter_col_validity(const dd_sorter *so, int32_t i) {
+    return i >= 0 && i < (int32_t)so->col_validity.size() ? so->col_validity[i] : nullptr;
+}
+
+extern "C" dd_status dd_sorter_info(const dd_sorter *so, int32_t *out4) {
+    if (!so || !out4) return set_err(DD_ERR_INVALID, "null argument");
+    memcpy(out4, so->info, sizeof(so->info));
+    return DD_OK;
+}
+
+extern "C" dd_status dd_sorter_kernel_ms(const dd_sorter *so, float *out4) {
+    if (!so || !out4) return set_err(DD_ERR_INVALID, "null argument");
+    memcpy(out4, so->kernel_ms, sizeof(so->kernel_ms));
+    return DD_OK;
+}
+
+extern "C" void dd_sorter_destroy(dd_sorter *so) { delete so; }
 
 /* ---------------- coalesce (dd_coalesce_run) ---------------- */
 

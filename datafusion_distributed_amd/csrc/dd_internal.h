@@ -52,6 +52,17 @@
 #define DD_J_SCAN_TILE 1024    /* scan: counts per block, 4 per thread */
 #define DD_J_SUMS_THREADS 1024 /* scan: tile sums per round of the one-block middle pass */
 
+/* sort / top-k above the shuffle (dd_sort.hip); the segment search and its
+ * LDS staging are the final merge's (DD_F_LDS_SEGS) */
+#define DD_S_MAX_KEYS 4
+#define DD_S_MAX_WORDS 9       /* four dec128 keys give 8 value words; + the meta word */
+#define DD_S_THREADS 256
+#define DD_S_TILE 2048         /* hist / scatter: rows per tile = 4 waves x 8 steps x 64 */
+#define DD_S_ENC_ROWS 16384    /* encode: rows per block, so a block's census flush of at
+                                  most 2048 bins per word is spread over 16384 rows */
+#define DD_S_SCAN_TILE 1024    /* scan: histogram entries per block, 4 per thread */
+#define DD_S_SUMS_THREADS 1024 /* scan: tile sums per round of the one-block middle pass */
+
 /* dtype codes mirror dd_dtype in include/dd_shuffle.h */
 enum {
     DD_KDT_U8 = 1,
@@ -135,6 +146,34 @@ struct dd_join_gather {
     const uint8_t *src_valid[DD_KMAX_COLS];   /* null: the column has no validity */
     void *dst[DD_KMAX_COLS];
     uint8_t *dst_valid[DD_KMAX_COLS];
+};
+
+/* the keys of a sort, passed by value to k_sort_encode. Word w of a row is the ordered
+ * value word wpart[w] (0: the only or high word, 1: a dec128's low word) of key wkey[w];
+ * the last word (n_words - 1) is the meta word: partition id << 32 | null rank of key j in
+ * byte j */
+struct dd_sort_keys {
+    int32_t n_keys;
+    int32_t n_words;
+    int32_t dtype[DD_S_MAX_KEYS];
+    int32_t flags[DD_S_MAX_KEYS]; /* DD_SORT_DESC | DD_SORT_NULLS_FIRST */
+    int32_t wkey[DD_S_MAX_WORDS];
+    int32_t wpart[DD_S_MAX_WORDS];
+    const void *data[DD_S_MAX_KEYS];
+    const uint8_t *valid[DD_S_MAX_KEYS]; /* null: the key has no validity */
+};
+
+/* the typed columns k_final_columns writes from a final merge's interleaved state */
+struct dd_final_cols {
+    int32_t n_keys;
+    int32_t n_aggs;
+    int32_t key_dtype[4];
+    int32_t ops[DD_F_MAX_AGGS];
+    void *key_data[4];
+    uint8_t *key_valid[4];
+    void *agg_data[DD_F_MAX_AGGS];
+    uint8_t *agg_valid[DD_F_MAX_AGGS]; /* null for COUNT, which is never NULL */
+    int64_t *nn_data[DD_F_MAX_AGGS];   /* null unless the nn columns were asked for */
 };
 
 /* dictionary GC (dd_dictgc.hip): one workgroup per row tile; a tile never straddles a
@@ -325,6 +364,26 @@ hipError_t dd_launch_final_merge(const dd_kargs *a, const dd_final_plan *plan,
                                  uint64_t *out_keys, uint32_t *out_keynull,
                                  uint64_t *out_aggs, uint64_t *out_hi, uint64_t *out_nn,
                                  hipStream_t s);
+/* typed device columns of a finished final merge (k_final_columns, dd_final.hip) */
+hipError_t dd_launch_final_columns(const dd_final_cols *c, int64_t n_groups,
+                                   const uint64_t *keys, const uint32_t *keynull,
+                                   const uint64_t *aggs, const uint64_t *hi,
+                                   const uint64_t *nn, hipStream_t s);
+/* sort (dd_sort.hip). words: u64[n_words][n]; census: u32[n_words][8][256], zeroed */
+hipError_t dd_launch_sort_encode(const dd_sort_keys *k, int64_t n, const int64_t *seg_offsets,
+                                 const int32_t *seg_part, int32_t n_segs, uint64_t *words,
+                                 uint32_t *perm, uint32_t *census, hipStream_t s);
+/* one stable pass on the digit (word >> shift) & 255. hist: u32[256 * tiles], tiles = n /
+ * DD_S_TILE rounded up; sums: u32[256 * tiles / DD_S_SCAN_TILE rounded up] */
+hipError_t dd_launch_sort_pass(const uint64_t *win, const uint32_t *pin, int64_t n, int shift,
+                               uint32_t *hist, uint32_t *sums, uint64_t *wout, uint32_t *pout,
+                               hipStream_t s);
+hipError_t dd_launch_sort_gather_word(const uint64_t *src, const uint32_t *perm, int64_t n,
+                                      uint64_t *out, hipStream_t s);
+/* in_off / out_off: device int64[n_parts + 1], sorted rows and kept rows before partition p */
+hipError_t dd_launch_sort_seg_out(const uint32_t *sorted, const int64_t *in_off,
+                                  const int64_t *out_off, int32_t n_parts, int64_t n_out,
+                                  uint32_t *perm_out, hipStream_t s);
 /* hash join (dd_join.hip). table: the build side's regions as in the final merge; next:
  * u32[build rows] preset to DD_F_EMPTY; the layout passed to build is the build side's, to
  * count / emit_probe the probe side's */

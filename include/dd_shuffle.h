@@ -670,7 +670,28 @@ dd_status dd_finalizer_fetch_nn(const dd_finalizer *f, uint64_t *host_nn);
 dd_status dd_finalizer_fetch_hi(const dd_finalizer *f, uint64_t *host_hi);
 /* same seam: hipEvent times of the run in ms: out3 = [claim, scan, merge] */
 dd_status dd_finalizer_kernel_ms(const dd_finalizer *f, float *out3);
-/* same seam: frees the merged rows */
+/* same seam: the merged rows as typed DEVICE columns, for a further operator on the device
+ * (DESIGN.md §18.6). Column order: n_keys key columns, each in its input dtype from the
+ * canonical key bits (so a float key comes out canonicalised: +0.0 for -0.0, one quiet NaN)
+ * with a validity buffer from keynull; n_aggs aggregate columns (COUNT, SUM_I64, MIN_I64,
+ * MAX_I64: i64; SUM_F64, MIN_F64, MAX_F64: f64; SUM_DEC128: dec128 = (lo, hi)) with a
+ * validity buffer nn != 0, none for COUNT; then, when with_nn, n_aggs i64 nn columns without
+ * validity. key_dtypes / agg_ops are the run's (the finalizer keeps no plan); counts that
+ * differ from the run's are DD_ERR_INVALID. Rows are the groups in dd_finalizer_fetch's
+ * order, partition-major by dd_finalizer_group_offsets. A second call replaces the columns.
+ * Synchronous on `stream`. */
+dd_status dd_finalizer_columns(dd_finalizer *f, const int32_t *key_dtypes, int32_t n_keys,
+                               const int32_t *agg_ops, int32_t n_aggs, int32_t with_nn,
+                               void *stream);
+/* same seam: columns built by dd_finalizer_columns (0 before it ran) */
+int32_t dd_finalizer_n_cols(const dd_finalizer *f);
+/* same seam: dd_dtype of column i */
+int32_t dd_finalizer_col_dtype(const dd_finalizer *f, int32_t i);
+/* same seam: device values of column i, owned by the finalizer; NULL at zero groups */
+const void *dd_finalizer_col_data(const dd_finalizer *f, int32_t i);
+/* same seam: device validity bytes of column i, NULL when it has none */
+const uint8_t *dd_finalizer_col_validity(const dd_finalizer *f, int32_t i);
+/* same seam: frees the merged rows and their columns */
 void dd_finalizer_destroy(dd_finalizer *f);
 
 /* ---------------- partitioned hash join (above two co-partitioned shuffles) ----------------
@@ -788,6 +809,71 @@ const uint8_t *dd_joiner_col_validity(const dd_joiner *j, int32_t i);
 dd_status dd_joiner_kernel_ms(const dd_joiner *j, float *out5);
 /* same seam: frees the join's output */
 void dd_joiner_destroy(dd_joiner *j);
+
+/* ---------------- sort / top-k per partition (above the shuffle) ----------------
+ * The SortExec: expr=[...], preserve_partitioning=[true] (TopK(fetch=k) under a LIMIT) that
+ * closes every task of the TPC-H plans: tests/tpch_plans_test.rs:30 (q1), :180 (q3), :853
+ * (q13), :1113 (q18), above AggregateExec mode=FinalPartitioned. DESIGN.md §22 is normative;
+ * datafusion_distributed_amd/sortref.py states the same rules in Python.
+ *
+ * Input: a device batch plus a segment layout in the final aggregation's form (above). A
+ * row's INPUT RANK is its row index. Keys: 1..4 of (column, flags), flags = DD_SORT_DESC |
+ * DD_SORT_NULLS_FIRST, the two independent; dtypes u8, bool, i16, i32, i64, f32, f64, dec128.
+ * Order of values: u8 / bool unsigned; integers signed; f32 / f64 IEEE-754 totalOrder on the
+ * RAW bit pattern (-0.0 < +0.0, a sign-clear NaN above +inf, a sign-set NaN below -inf, NaN
+ * payloads by their bits: arrow-rs total_cmp; nothing is canonicalised); dec128 signed 128-bit.
+ * NULLs are equal to each other and their value bytes are never read. DESC reverses the
+ * values only; NULLS_FIRST alone places the NULLs.
+ *
+ * Output: one segment per partition (n_parts segments, seg_part = identity), partition-major;
+ * partition p holds its rows in key order, ties in input rank (the sort is STABLE, so every
+ * bit of the output is determined). fetch = k >= 0 keeps the first min(k, rows) rows of each
+ * partition, fetch = -1 all; fetch = 0 is a valid empty result. The result holds perm (the
+ * source row of each output row), the proj columns gathered on the device (fixed-width dtypes
+ * of 1, 2, 4, 8 or 16 byte elements; validity exactly when the source has it) and the new
+ * seg_offsets. The SortPreservingMergeExec(fetch=k) on top of the plan is this entry again
+ * over the result with the one-partition layout ([0, n_out], [0], 1): its stable tie order is
+ * partition order, the order a merge takes ties in.
+ *
+ * Every check runs before any device work. DD_ERR_UNSUPPORTED: a dict32 key (dictionary
+ * index order is not value order), a utf8 / utf8view key, a utf8 / dict32 column in proj.
+ * DD_ERR_INVALID: 0 keys or more than 4, a column index out of range, unknown flag bits,
+ * fetch < -1, a malformed layout (dd_final_merge_run's checks), n_rows >= 2^31 (perm holds
+ * 32-bit row ids). n_rows == 0 succeeds with empty segments. DD_SORT_SKIP=0 (environment,
+ * read per call) runs every planned radix pass instead of dropping those whose digit is the
+ * same in all rows; results are bit-identical. Synchronous on `stream`. */
+
+#define DD_SORT_DESC 1
+#define DD_SORT_NULLS_FIRST 2
+
+typedef struct dd_sorter dd_sorter; /* opaque: perm, gathered columns, segment offsets */
+
+/* seam: SortExec preserve_partitioning=[true] above AggregateExec mode=FinalPartitioned
+ * (tests/tpch_plans_test.rs:180, :1113); with the one-partition layout, the
+ * SortPreservingMergeExec above it (:175, :1109) */
+dd_status dd_sort_run(const dd_batch_desc *batch, const int32_t *key_cols,
+                      const int32_t *key_flags, int32_t n_keys, const int32_t *proj_cols,
+                      int32_t n_proj, const int64_t *seg_offsets, const int32_t *seg_part,
+                      int32_t n_segs, int32_t n_parts, int64_t fetch, void *stream,
+                      dd_sorter **out);
+/* same seam: output rows of the SortExec, after fetch */
+int64_t dd_sorter_n_rows(const dd_sorter *s);
+/* same seam: host_out[n_parts + 1]: partition p's rows are [out[p], out[p + 1]) */
+dd_status dd_sorter_seg_offsets(const dd_sorter *s, int64_t *host_out);
+/* same seam: device u32[n_rows], the input row of each output row; NULL at zero rows */
+const uint32_t *dd_sorter_perm(const dd_sorter *s);
+/* same seam: device values of projected column i, in output order; NULL at zero rows */
+const void *dd_sorter_col_data(const dd_sorter *s, int32_t i);
+/* same seam: device validity bytes of projected column i, NULL when its source has none */
+const uint8_t *dd_sorter_col_validity(const dd_sorter *s, int32_t i);
+/* same seam: out4 = [radix passes planned from the key dtypes and the layout, passes run
+ * after the census dropped the constant digits, rows per scatter tile, 64-bit words per row
+ * (ordered key words + the partition / null-rank word)] */
+dd_status dd_sorter_info(const dd_sorter *s, int32_t *out4);
+/* same seam: hipEvent times in ms: out4 = [encode + census, passes, segment output, gather] */
+dd_status dd_sorter_kernel_ms(const dd_sorter *s, float *out4);
+/* same seam: frees the sort's output */
+void dd_sorter_destroy(dd_sorter *s);
 
 /* ---------------- device helpers (harness convenience; not part of the seam) ------- */
 dd_status dd_dev_alloc(int64_t bytes, void **out);
