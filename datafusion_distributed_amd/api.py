@@ -1072,45 +1072,108 @@ def final_merge(batch: DeviceBatch, key_idx, aggs, seg_offsets=None, seg_part=No
     u64[n, na], "group_offsets": i64[n_parts + 1] (partition p's groups are rows
     [off[p], off[p + 1]); their order inside a partition is unspecified), "kernel_ms":
     [claim, scan, merge]}."""
-    nk = len(key_idx)
-    na = len(aggs)
-    if seg_offsets is None:
-        seg_offsets, seg_part, n_parts = [0, batch.n_rows], [0], 1
-    off = np.ascontiguousarray(seg_offsets, dtype=np.int64)
-    part = np.ascontiguousarray(seg_part, dtype=np.int32)
-    if len(off) != len(part) + 1:
-        raise ValueError("final_merge: seg_offsets must have one entry more than seg_part")
-    keysc = (ctypes.c_int32 * max(nk, 1))(*key_idx)
-    statec = (ctypes.c_int32 * max(na, 1))(*[c for c, _, _ in aggs])
-    opsc = (ctypes.c_int32 * max(na, 1))(*[AGG_OPS[o] for _, o, _ in aggs])
-    nnc = (ctypes.c_int32 * max(na, 1))(*[-1 if c is None else c for _, _, c in aggs])
-    h = ctypes.c_void_p()
-    _check(lib().dd_final_merge_run(
-        ctypes.byref(batch.desc), keysc, nk, statec, opsc, nnc, na,
-        off.ctypes.data_as(ctypes.c_void_p), part.ctypes.data_as(ctypes.c_void_p),
-        ctypes.c_int32(len(part)), ctypes.c_int32(n_parts), None, ctypes.byref(h)))
+    h, _, n_parts = _run_final_merge("final_merge", batch, key_idx, aggs, seg_offsets, seg_part,
+                                     n_parts)
     try:
-        n = int(lib().dd_finalizer_n_groups(h))
-        keys = np.zeros((n, nk), dtype=np.uint64)
-        keynull = np.zeros(n, dtype=np.uint32)
-        vals = np.zeros((n, na), dtype=np.float64)
-        nn = np.zeros((n, na), dtype=np.uint64)
-        hi = np.zeros((n, na), dtype=np.uint64)
-        goff = np.zeros(n_parts + 1, dtype=np.int64)
-        ms = (ctypes.c_float * 3)()
-        _check(lib().dd_finalizer_group_offsets(h, goff.ctypes.data_as(ctypes.c_void_p)))
-        _check(lib().dd_finalizer_kernel_ms(h, ms))
-        if n:
-            _check(lib().dd_finalizer_fetch(
-                h, keys.ctypes.data_as(ctypes.c_void_p),
-                keynull.ctypes.data_as(ctypes.c_void_p),
-                vals.ctypes.data_as(ctypes.c_void_p)))
-            _check(lib().dd_finalizer_fetch_nn(h, nn.ctypes.data_as(ctypes.c_void_p)))
-            _check(lib().dd_finalizer_fetch_hi(h, hi.ctypes.data_as(ctypes.c_void_p)))
-        return {"keys": keys, "keynull": keynull, "aggs": vals, "aggs_hi": hi, "nn": nn,
-                "group_offsets": goff, "kernel_ms": list(ms)}
+        return _fetch_merged(h, len(key_idx), len(aggs), n_parts)
     finally:
         lib().dd_finalizer_destroy(h)
+
+
+def _layout(who, layout, n_rows):
+    """(seg_offsets i64[S + 1], seg_part i32[S], n_parts) of a {"seg_offsets", "seg_part",
+    "n_parts"} layout, None being one segment and one partition over n_rows rows. `who`
+    names the caller in the ValueError."""
+    if layout is None:
+        layout = {"seg_offsets": [0, n_rows], "seg_part": [0], "n_parts": 1}
+    off = np.ascontiguousarray(layout["seg_offsets"], dtype=np.int64)
+    part = np.ascontiguousarray(layout["seg_part"], dtype=np.int32)
+    if len(off) != len(part) + 1:
+        raise ValueError(f"{who}: seg_offsets must have one entry more than seg_part")
+    return off, part, int(layout["n_parts"])
+
+
+def _i32s(vals):
+    return (ctypes.c_int32 * max(len(vals), 1))(*vals)
+
+
+def _layout_args(off, part, n_parts):
+    return (off.ctypes.data_as(ctypes.c_void_p), part.ctypes.data_as(ctypes.c_void_p),
+            ctypes.c_int32(len(part)), ctypes.c_int32(n_parts))
+
+
+def _run_final_merge(who, batch, key_idx, aggs, seg_offsets, seg_part, n_parts):
+    """Marshal final_merge's arguments and run dd_final_merge_run: (handle, ops as a C array,
+    n_parts of the layout used)."""
+    layout = None if seg_offsets is None else {"seg_offsets": seg_offsets,
+                                               "seg_part": seg_part, "n_parts": n_parts}
+    off, part, n_parts = _layout(who, layout, batch.n_rows)
+    opsc = _i32s([AGG_OPS[o] for _, o, _ in aggs])
+    h = ctypes.c_void_p()
+    _check(lib().dd_final_merge_run(
+        ctypes.byref(batch.desc), _i32s(key_idx), len(key_idx),
+        _i32s([c for c, _, _ in aggs]), opsc, _i32s([-1 if c is None else c for _, _, c in aggs]),
+        len(aggs), *_layout_args(off, part, n_parts), None, ctypes.byref(h)))
+    return h, opsc, n_parts
+
+
+def _fetch_merged(h, nk, na, n_parts):
+    """final_merge's result dict: host copies of a finalizer's interleaved state."""
+    n = int(lib().dd_finalizer_n_groups(h))
+    keys = np.zeros((n, nk), dtype=np.uint64)
+    keynull = np.zeros(n, dtype=np.uint32)
+    vals = np.zeros((n, na), dtype=np.float64)
+    nn = np.zeros((n, na), dtype=np.uint64)
+    hi = np.zeros((n, na), dtype=np.uint64)
+    goff = np.zeros(n_parts + 1, dtype=np.int64)
+    ms = (ctypes.c_float * 3)()
+    _check(lib().dd_finalizer_group_offsets(h, goff.ctypes.data_as(ctypes.c_void_p)))
+    _check(lib().dd_finalizer_kernel_ms(h, ms))
+    if n:
+        _check(lib().dd_finalizer_fetch(
+            h, keys.ctypes.data_as(ctypes.c_void_p), keynull.ctypes.data_as(ctypes.c_void_p),
+            vals.ctypes.data_as(ctypes.c_void_p)))
+        _check(lib().dd_finalizer_fetch_nn(h, nn.ctypes.data_as(ctypes.c_void_p)))
+        _check(lib().dd_finalizer_fetch_hi(h, hi.ctypes.data_as(ctypes.c_void_p)))
+    return {"keys": keys, "keynull": keynull, "aggs": vals, "aggs_hi": hi, "nn": nn,
+            "group_offsets": goff, "kernel_ms": list(ms)}
+
+
+class _DeviceColumns:
+    """What Joined, Sorted and Merged share: typed output columns on the device, owned by a
+    library handle. A subclass names its accessor and destroy symbols; _out_cols holds
+    (dtype, has validity) per column."""
+
+    _COL_DATA = _COL_VALIDITY = _DESTROY = None
+
+    def __init__(self, h, out_cols, n_rows):
+        self.h = h
+        self._out_cols = out_cols
+        self.n_rows = n_rows
+
+    def _views(self):
+        """The columns as DeviceBatch.from_device takes them; nothing is copied."""
+        data, valid = getattr(lib(), self._COL_DATA), getattr(lib(), self._COL_VALIDITY)
+        return [{"dtype": dt, "data_ptr": data(self.h, i), "valid_ptr": valid(self.h, i)}
+                for i, (dt, _) in enumerate(self._out_cols)]
+
+    def col(self, i):
+        """Host copy of output column i in Partitioner.col_out's shape (tests)."""
+        dt, has_valid = self._out_cols[i]
+        n = self.n_rows
+        res = {"dtype": dt, "data": fixed_out(dt, np.zeros(0, dtype=FIXED_NP[dt]))}
+        if n:
+            res["data"] = fixed_out(dt, _d2h(getattr(lib(), self._COL_DATA)(self.h, i),
+                                             n * ELEM_SIZE[dt], FIXED_NP[dt]))
+        if has_valid:
+            res["valid"] = (_d2h(getattr(lib(), self._COL_VALIDITY)(self.h, i), n, np.uint8)
+                            if n else np.zeros(0, dtype=np.uint8))
+        return res
+
+    def destroy(self):
+        if self.h:
+            getattr(lib(), self._DESTROY)(self.h)
+            self.h = None
 
 
 def _output_view(src, col_data, col_validity, n_rows):
@@ -1159,17 +1222,18 @@ JOIN_TYPES = {"inner": 0, "left_semi": 1, "left_anti": 2, "right_semi": 3, "righ
               "left": 5, "right": 6, "full": 7}
 
 
-class Joined:
+class Joined(_DeviceColumns):
     """Output of hash_join (dd_joiner_*): pair indices and the projected columns, all on
     the device, plus the emitting side's segment layout with new offsets."""
 
+    _COL_DATA, _COL_VALIDITY = "dd_joiner_col_data", "dd_joiner_col_validity"
+    _DESTROY = "dd_joiner_destroy"
+
     def __init__(self, h, join_type, out_cols, seg_part, n_parts):
-        self.h = h
+        super().__init__(h, out_cols, int(lib().dd_joiner_n_rows(h)))
         self.join_type = join_type
-        self._out_cols = out_cols  # (dtype, source has validity) per output column
         self._seg_part = seg_part
         self._n_parts = n_parts
-        self.n_rows = int(lib().dd_joiner_n_rows(h))
 
     def seg_offsets(self):
         """Host i64[S + 1] over the output rows; S and seg_part are the emitting side's."""
@@ -1202,24 +1266,7 @@ class Joined:
         partial_reduce or Partitioner. Nothing is copied; this Joined must outlive it."""
         if not self._out_cols:
             raise ValueError("hash_join: no projected columns, so there is no batch (pairs only)")
-        L = lib()
-        view = [{"dtype": dt, "data_ptr": L.dd_joiner_col_data(self.h, i),
-                 "valid_ptr": L.dd_joiner_col_validity(self.h, i)}
-                for i, (dt, _) in enumerate(self._out_cols)]
-        return DeviceBatch.from_device(view, self.n_rows), self.layout()
-
-    def col(self, i):
-        """Host copy of output column i in Partitioner.col_out's shape (tests)."""
-        dt, has_valid = self._out_cols[i]
-        n = self.n_rows
-        res = {"dtype": dt, "data": fixed_out(dt, np.zeros(0, dtype=FIXED_NP[dt]))}
-        if n:
-            res["data"] = fixed_out(dt, _d2h(lib().dd_joiner_col_data(self.h, i),
-                                             n * ELEM_SIZE[dt], FIXED_NP[dt]))
-        if has_valid:
-            res["valid"] = (_d2h(lib().dd_joiner_col_validity(self.h, i), n, np.uint8) if n
-                            else np.zeros(0, dtype=np.uint8))
-        return res
+        return DeviceBatch.from_device(self._views(), self.n_rows), self.layout()
 
     def kernel_ms(self):
         """[build, count, scan, emit, gather] hipEvent times in ms."""
@@ -1227,20 +1274,21 @@ class Joined:
         _check(lib().dd_joiner_kernel_ms(self.h, out))
         return list(out)
 
-    def destroy(self):
-        if self.h:
-            lib().dd_joiner_destroy(self.h)
-            self.h = None
 
-
-def _join_layout(layout, n_rows):
-    if layout is None:
-        layout = {"seg_offsets": [0, n_rows], "seg_part": [0], "n_parts": 1}
-    off = np.ascontiguousarray(layout["seg_offsets"], dtype=np.int64)
-    part = np.ascontiguousarray(layout["seg_part"], dtype=np.int32)
-    if len(off) != len(part) + 1:
-        raise ValueError("hash_join: seg_offsets must have one entry more than seg_part")
-    return off, part, int(layout["n_parts"])
+def _run_join(entry, build, build_keys, probe, probe_keys, join_type, build_layout,
+              probe_layout, build_proj, probe_proj):
+    """Marshal a join's arguments and run `entry` (dd_hash_join_run or its outer twin):
+    (handle, build seg_part, probe seg_part, n_parts)."""
+    boff, bpart, bparts = _layout("hash_join", build_layout, build.n_rows)
+    poff, ppart, pparts = _layout("hash_join", probe_layout, probe.n_rows)
+    h = ctypes.c_void_p()
+    _check(getattr(lib(), entry)(
+        ctypes.byref(build.desc), _i32s(build_keys), ctypes.byref(probe.desc),
+        _i32s(probe_keys), ctypes.c_int32(len(build_keys)),
+        ctypes.c_int32(JOIN_TYPES[join_type]), *_layout_args(boff, bpart, bparts),
+        *_layout_args(poff, ppart, pparts), _i32s(build_proj), ctypes.c_int32(len(build_proj)),
+        _i32s(probe_proj), ctypes.c_int32(len(probe_proj)), None, ctypes.byref(h)))
+    return h, bpart, ppart, bparts
 
 
 def hash_join(build: DeviceBatch, build_keys, probe: DeviceBatch, probe_keys,
@@ -1264,29 +1312,15 @@ def hash_join(build: DeviceBatch, build_keys, probe: DeviceBatch, probe_keys,
         raise ValueError(f"hash_join: unknown join type {join_type!r}")
     if len(build_keys) != len(probe_keys):
         raise ValueError("hash_join: the two sides need the same number of key columns")
-    nk = len(build_keys)
     emits_build = not join_type.startswith("right_")
     emits_probe = not join_type.startswith("left_")
     if build_proj is None:
         build_proj = list(range(build.desc.n_cols)) if emits_build else []
     if probe_proj is None:
         probe_proj = list(range(probe.desc.n_cols)) if emits_probe else []
-    boff, bpart, bparts = _join_layout(build_layout, build.n_rows)
-    poff, ppart, pparts = _join_layout(probe_layout, probe.n_rows)
-    bk = (ctypes.c_int32 * max(nk, 1))(*build_keys)
-    pk = (ctypes.c_int32 * max(nk, 1))(*probe_keys)
-    bp = (ctypes.c_int32 * max(len(build_proj), 1))(*build_proj)
-    pp = (ctypes.c_int32 * max(len(probe_proj), 1))(*probe_proj)
-    h = ctypes.c_void_p()
-    _check(lib().dd_hash_join_run(
-        ctypes.byref(build.desc), bk, ctypes.byref(probe.desc), pk, ctypes.c_int32(nk),
-        ctypes.c_int32(JOIN_TYPES[join_type]),
-        boff.ctypes.data_as(ctypes.c_void_p), bpart.ctypes.data_as(ctypes.c_void_p),
-        ctypes.c_int32(len(bpart)), ctypes.c_int32(bparts),
-        poff.ctypes.data_as(ctypes.c_void_p), ppart.ctypes.data_as(ctypes.c_void_p),
-        ctypes.c_int32(len(ppart)), ctypes.c_int32(pparts),
-        bp, ctypes.c_int32(len(build_proj)), pp, ctypes.c_int32(len(probe_proj)),
-        None, ctypes.byref(h)))
+    h, bpart, ppart, bparts = _run_join("dd_hash_join_run", build, build_keys, probe,
+                                        probe_keys, join_type, build_layout, probe_layout,
+                                        build_proj, probe_proj)
     out_cols = [(b.cols[i]["dtype"], bool(b.desc.cols[i].validity))
                 for b, proj in ((build, build_proj), (probe, probe_proj)) for i in proj]
     return Joined(h, join_type, out_cols, ppart if emits_probe else bpart, bparts)
@@ -1316,28 +1350,14 @@ def outer_join(build: DeviceBatch, build_keys, probe: DeviceBatch, probe_keys, j
         raise ValueError(f"outer_join: unknown join type {join_type!r}")
     if len(build_keys) != len(probe_keys):
         raise ValueError("outer_join: the two sides need the same number of key columns")
-    nk = len(build_keys)
     if build_proj is None:
         build_proj = list(range(build.desc.n_cols))
     if probe_proj is None:
         probe_proj = list(range(probe.desc.n_cols))
-    boff, bpart, bparts = _join_layout(build_layout, build.n_rows)
-    poff, ppart, pparts = _join_layout(probe_layout, probe.n_rows)
-    bk = (ctypes.c_int32 * max(nk, 1))(*build_keys)
-    pk = (ctypes.c_int32 * max(nk, 1))(*probe_keys)
-    bp = (ctypes.c_int32 * max(len(build_proj), 1))(*build_proj)
-    pp = (ctypes.c_int32 * max(len(probe_proj), 1))(*probe_proj)
-    h = ctypes.c_void_p()
     # the five other types reach the library too: it refuses them and names hash_join's entry
-    _check(lib().dd_hash_join_outer_run(
-        ctypes.byref(build.desc), bk, ctypes.byref(probe.desc), pk, ctypes.c_int32(nk),
-        ctypes.c_int32(JOIN_TYPES[join_type]),
-        boff.ctypes.data_as(ctypes.c_void_p), bpart.ctypes.data_as(ctypes.c_void_p),
-        ctypes.c_int32(len(bpart)), ctypes.c_int32(bparts),
-        poff.ctypes.data_as(ctypes.c_void_p), ppart.ctypes.data_as(ctypes.c_void_p),
-        ctypes.c_int32(len(ppart)), ctypes.c_int32(pparts),
-        bp, ctypes.c_int32(len(build_proj)), pp, ctypes.c_int32(len(probe_proj)),
-        None, ctypes.byref(h)))
+    h, bpart, ppart, bparts = _run_join("dd_hash_join_outer_run", build, build_keys, probe,
+                                        probe_keys, join_type, build_layout, probe_layout,
+                                        build_proj, probe_proj)
     null_ext = {"left": (False, True), "right": (True, False), "full": (True, True)}[join_type]
     out_cols = [(b.cols[i]["dtype"], ext or bool(b.desc.cols[i].validity))
                 for b, proj, ext in ((build, build_proj, null_ext[0]),
@@ -1348,12 +1368,14 @@ def outer_join(build: DeviceBatch, build_keys, probe: DeviceBatch, probe_keys, j
     return joined
 
 
-class Merged:
+class Merged(_DeviceColumns):
     """Output of final_merge_device (dd_finalizer_*): the merged rows kept on the device as
     typed columns, for a further operator."""
 
+    _COL_DATA, _COL_VALIDITY = "dd_finalizer_col_data", "dd_finalizer_col_validity"
+    _DESTROY = "dd_finalizer_destroy"
+
     def __init__(self, h, key_dtypes, ops, n_parts, with_nn):
-        self.h = h
         self.key_dtypes = list(key_dtypes)
         self.ops = list(ops)
         self.n_parts = n_parts
@@ -1362,6 +1384,10 @@ class Merged:
         self.n_cols = int(lib().dd_finalizer_n_cols(h))
         inv = {v: k for k, v in DTYPE_CODE.items()}
         self.dtypes = [inv[int(lib().dd_finalizer_col_dtype(h, i))] for i in range(self.n_cols)]
+        # keys are nullable, every aggregate but count is, the nn columns are not
+        has_valid = [True] * len(self.key_dtypes) + [o != "count" for o in self.ops]
+        has_valid += [False] * (self.n_cols - len(has_valid))
+        super().__init__(h, list(zip(self.dtypes, has_valid)), self.n_groups)
 
     def group_offsets(self):
         """Host i64[n_parts + 1]: partition p's groups are rows [off[p], off[p + 1])."""
@@ -1378,50 +1404,12 @@ class Merged:
         per aggregate, then the nn columns if asked for) plus the layout with seg_offsets =
         group_offsets and identity seg_part, ready for sort_topk, Partitioner, partial_reduce,
         final_merge or a join. Nothing is copied; this Merged must outlive it."""
-        L = lib()
-        view = [{"dtype": dt, "data_ptr": L.dd_finalizer_col_data(self.h, i),
-                 "valid_ptr": L.dd_finalizer_col_validity(self.h, i)}
-                for i, dt in enumerate(self.dtypes)]
-        return DeviceBatch.from_device(view, self.n_groups), self.layout()
-
-    def col(self, i):
-        """Host copy of column i in Partitioner.col_out's shape (tests)."""
-        dt, n = self.dtypes[i], self.n_groups
-        res = {"dtype": dt, "data": fixed_out(dt, np.zeros(0, dtype=FIXED_NP[dt]))}
-        if n:
-            res["data"] = fixed_out(dt, _d2h(lib().dd_finalizer_col_data(self.h, i),
-                                             n * ELEM_SIZE[dt], FIXED_NP[dt]))
-        vp = lib().dd_finalizer_col_validity(self.h, i)
-        has_valid = i < len(self.key_dtypes) + len(self.ops) and not (
-            i >= len(self.key_dtypes) and self.ops[i - len(self.key_dtypes)] == "count")
-        if has_valid:
-            res["valid"] = _d2h(vp, n, np.uint8) if n else np.zeros(0, dtype=np.uint8)
-        return res
+        return DeviceBatch.from_device(self._views(), self.n_groups), self.layout()
 
     def fetch(self):
         """The dict final_merge returns for the same input (host copies of the interleaved
         state), so a test can hold the columns to it."""
-        n, nk, na = self.n_groups, len(self.key_dtypes), len(self.ops)
-        keys = np.zeros((n, nk), dtype=np.uint64)
-        keynull = np.zeros(n, dtype=np.uint32)
-        vals = np.zeros((n, na), dtype=np.float64)
-        nn = np.zeros((n, na), dtype=np.uint64)
-        hi = np.zeros((n, na), dtype=np.uint64)
-        ms = (ctypes.c_float * 3)()
-        _check(lib().dd_finalizer_kernel_ms(self.h, ms))
-        if n:
-            _check(lib().dd_finalizer_fetch(
-                self.h, keys.ctypes.data_as(ctypes.c_void_p),
-                keynull.ctypes.data_as(ctypes.c_void_p), vals.ctypes.data_as(ctypes.c_void_p)))
-            _check(lib().dd_finalizer_fetch_nn(self.h, nn.ctypes.data_as(ctypes.c_void_p)))
-            _check(lib().dd_finalizer_fetch_hi(self.h, hi.ctypes.data_as(ctypes.c_void_p)))
-        return {"keys": keys, "keynull": keynull, "aggs": vals, "aggs_hi": hi, "nn": nn,
-                "group_offsets": self.group_offsets(), "kernel_ms": list(ms)}
-
-    def destroy(self):
-        if self.h:
-            lib().dd_finalizer_destroy(self.h)
-            self.h = None
+        return _fetch_merged(self.h, len(self.key_dtypes), len(self.ops), self.n_parts)
 
 
 def final_merge_device(batch: DeviceBatch, key_idx, aggs, seg_offsets=None, seg_part=None,
@@ -1436,49 +1424,33 @@ def final_merge_device(batch: DeviceBatch, key_idx, aggs, seg_offsets=None, seg_
     min_f64 / max_f64, dec128 for sum_dec128, with validity nn != 0 (a total nn of 0 is SQL
     NULL; count has no validity buffer and is never NULL); with_nn adds one i64 nn column per
     aggregate after the value columns."""
-    nk = len(key_idx)
-    na = len(aggs)
-    if seg_offsets is None:
-        seg_offsets, seg_part, n_parts = [0, batch.n_rows], [0], 1
-    off = np.ascontiguousarray(seg_offsets, dtype=np.int64)
-    part = np.ascontiguousarray(seg_part, dtype=np.int32)
-    if len(off) != len(part) + 1:
-        raise ValueError("final_merge_device: seg_offsets must have one entry more than "
-                         "seg_part")
-    keysc = (ctypes.c_int32 * max(nk, 1))(*key_idx)
-    statec = (ctypes.c_int32 * max(na, 1))(*[c for c, _, _ in aggs])
-    opsc = (ctypes.c_int32 * max(na, 1))(*[AGG_OPS[o] for _, o, _ in aggs])
-    nnc = (ctypes.c_int32 * max(na, 1))(*[-1 if c is None else c for _, _, c in aggs])
-    h = ctypes.c_void_p()
-    _check(lib().dd_final_merge_run(
-        ctypes.byref(batch.desc), keysc, nk, statec, opsc, nnc, na,
-        off.ctypes.data_as(ctypes.c_void_p), part.ctypes.data_as(ctypes.c_void_p),
-        ctypes.c_int32(len(part)), ctypes.c_int32(n_parts), None, ctypes.byref(h)))
+    h, opsc, n_parts = _run_final_merge("final_merge_device", batch, key_idx, aggs, seg_offsets,
+                                        seg_part, n_parts)
     try:
         key_dtypes = [batch.cols[k]["dtype"] for k in key_idx]
-        kdt = (ctypes.c_int32 * max(nk, 1))(*[DTYPE_CODE[d] for d in key_dtypes])
-        _check(lib().dd_finalizer_columns(h, kdt, ctypes.c_int32(nk), opsc,
-                                          ctypes.c_int32(na), ctypes.c_int32(int(with_nn)),
-                                          None))
+        _check(lib().dd_finalizer_columns(
+            h, _i32s([DTYPE_CODE[d] for d in key_dtypes]), ctypes.c_int32(len(key_idx)), opsc,
+            ctypes.c_int32(len(aggs)), ctypes.c_int32(int(with_nn)), None))
     except Exception:
         lib().dd_finalizer_destroy(h)
         raise
-    return Merged(h, key_dtypes, [o for _, o, _ in aggs], int(n_parts), bool(with_nn))
+    return Merged(h, key_dtypes, [o for _, o, _ in aggs], n_parts, bool(with_nn))
 
 
 SORT_DESC = 1         # DD_SORT_DESC
 SORT_NULLS_FIRST = 2  # DD_SORT_NULLS_FIRST
 
 
-class Sorted:
+class Sorted(_DeviceColumns):
     """Output of sort_topk (dd_sorter_*): perm, the gathered columns and the new segment
     offsets, all on the device; one segment per partition."""
 
+    _COL_DATA, _COL_VALIDITY = "dd_sorter_col_data", "dd_sorter_col_validity"
+    _DESTROY = "dd_sorter_destroy"
+
     def __init__(self, h, out_cols, n_parts):
-        self.h = h
-        self._out_cols = out_cols  # (dtype, source has validity) per projected column
+        super().__init__(h, out_cols, int(lib().dd_sorter_n_rows(h)))
         self._n_parts = n_parts
-        self.n_rows = int(lib().dd_sorter_n_rows(h))
 
     def seg_offsets(self):
         """Host i64[n_parts + 1]: partition p's rows are [off[p], off[p + 1])."""
@@ -1508,24 +1480,7 @@ class Sorted:
         it."""
         if not self._out_cols:
             raise ValueError("sort_topk: no projected columns, so there is no batch (perm only)")
-        L = lib()
-        view = [{"dtype": dt, "data_ptr": L.dd_sorter_col_data(self.h, i),
-                 "valid_ptr": L.dd_sorter_col_validity(self.h, i)}
-                for i, (dt, _) in enumerate(self._out_cols)]
-        return DeviceBatch.from_device(view, self.n_rows), self.layout()
-
-    def col(self, i):
-        """Host copy of projected column i in Partitioner.col_out's shape (tests)."""
-        dt, has_valid = self._out_cols[i]
-        n = self.n_rows
-        res = {"dtype": dt, "data": fixed_out(dt, np.zeros(0, dtype=FIXED_NP[dt]))}
-        if n:
-            res["data"] = fixed_out(dt, _d2h(lib().dd_sorter_col_data(self.h, i),
-                                             n * ELEM_SIZE[dt], FIXED_NP[dt]))
-        if has_valid:
-            res["valid"] = (_d2h(lib().dd_sorter_col_validity(self.h, i), n, np.uint8) if n
-                            else np.zeros(0, dtype=np.uint8))
-        return res
+        return DeviceBatch.from_device(self._views(), self.n_rows), self.layout()
 
     def info(self):
         """{"passes_planned": radix passes the key dtypes and the layout call for,
@@ -1542,11 +1497,6 @@ class Sorted:
         out = (ctypes.c_float * 4)()
         _check(lib().dd_sorter_kernel_ms(self.h, out))
         return list(out)
-
-    def destroy(self):
-        if self.h:
-            lib().dd_sorter_destroy(self.h)
-            self.h = None
 
 
 def sort_topk(batch: DeviceBatch, keys, layout=None, fetch=None, proj=None):
@@ -1572,25 +1522,14 @@ def sort_topk(batch: DeviceBatch, keys, layout=None, fetch=None, proj=None):
     if proj is None:
         proj = list(range(batch.desc.n_cols))
     proj = [int(c) for c in proj]
-    if layout is None:
-        layout = {"seg_offsets": [0, batch.n_rows], "seg_part": [0], "n_parts": 1}
-    off = np.ascontiguousarray(layout["seg_offsets"], dtype=np.int64)
-    part = np.ascontiguousarray(layout["seg_part"], dtype=np.int32)
-    n_parts = int(layout["n_parts"])
-    if len(off) != len(part) + 1:
-        raise ValueError("sort_topk: seg_offsets must have one entry more than seg_part")
+    off, part, n_parts = _layout("sort_topk", layout, batch.n_rows)
     # None is the library's -1; a negative fetch reaches it as one it refuses
     fetch_c = -1 if fetch is None else int(fetch) if fetch >= 0 else min(int(fetch), -2)
-    nk = len(keys)
-    kc = (ctypes.c_int32 * max(nk, 1))(*[c for c, _, _ in keys])
-    kf = (ctypes.c_int32 * max(nk, 1))(*[(SORT_DESC if d else 0) | (SORT_NULLS_FIRST if nf else 0)
-                                         for _, d, nf in keys])
-    pc = (ctypes.c_int32 * max(len(proj), 1))(*proj)
+    kf = [(SORT_DESC if d else 0) | (SORT_NULLS_FIRST if nf else 0) for _, d, nf in keys]
     h = ctypes.c_void_p()
     _check(lib().dd_sort_run(
-        ctypes.byref(batch.desc), kc, kf, ctypes.c_int32(nk), pc, ctypes.c_int32(len(proj)),
-        off.ctypes.data_as(ctypes.c_void_p), part.ctypes.data_as(ctypes.c_void_p),
-        ctypes.c_int32(len(part)), ctypes.c_int32(n_parts),
-        ctypes.c_int64(fetch_c), None, ctypes.byref(h)))
+        ctypes.byref(batch.desc), _i32s([c for c, _, _ in keys]), _i32s(kf),
+        ctypes.c_int32(len(keys)), _i32s(proj), ctypes.c_int32(len(proj)),
+        *_layout_args(off, part, n_parts), ctypes.c_int64(fetch_c), None, ctypes.byref(h)))
     out_cols = [(batch.cols[i]["dtype"], bool(batch.desc.cols[i].validity)) for i in proj]
     return Sorted(h, out_cols, n_parts)

@@ -2159,6 +2159,169 @@ extern "C" dd_status dd_exchanged_stats(const dd_exchanged *e, float *ms,
     return DD_OK;
 }
 
+/* ---------------- host plumbing the operators share ---------------- */
+/* partial reduce, final merge, both joins and the sort: what they check and set up alike.
+ * Every check here runs before any device work and opens its message with the caller's
+ * prefix. */
+
+/* kernel arguments over a batch as it is: fixed-width keys, no dictionary hashes */
+static void dd_fill_kargs(const dd_batch_desc *b, const int32_t *keys, int32_t n_keys,
+                          dd_kargs *ka) {
+    memset(ka, 0, sizeof(*ka));
+    ka->n_rows = b->n_rows;
+    ka->n_cols = b->n_cols;
+    ka->n_keys = n_keys;
+    for (int k = 0; k < n_keys; k++) ka->key_idx[k] = keys[k];
+    for (int c = 0; c < b->n_cols; c++) {
+        const dd_col_desc &cd = b->cols[c];
+        dd_kcol &kc = ka->cols[c];
+        kc.dtype = cd.dtype;
+        kc.elem = fixed_elem_size(cd.dtype);
+        kc.data = cd.data;
+        kc.valid = cd.validity;
+        kc.offsets = cd.offsets;
+    }
+}
+
+/* frees every device pointer handed to it when it goes out of scope */
+struct dd_dev_scratch {
+    std::vector<void *> ptrs;
+    template <typename T> bool alloc(T **p, size_t bytes) {
+        void *v = nullptr;
+        if (hipMalloc(&v, bytes ? bytes : 1) != hipSuccess) return false;
+        ptrs.push_back(v);
+        *p = (T *)v;
+        return true;
+    }
+    /* alloc, then enqueue the copy of the host array src[n]. src is pageable: the caller
+     * synchronises the stream once, after its last upload and before src dies */
+    template <typename T> hipError_t upload(T **p, const T *src, size_t n, hipStream_t s) {
+        if (!alloc(p, n * sizeof(T))) return hipErrorOutOfMemory;
+        return hipMemcpyAsync(*p, src, n * sizeof(T), hipMemcpyHostToDevice, s);
+    }
+    ~dd_dev_scratch() {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+};
+
+/* N events, created by init() and destroyed on every exit path */
+template <int N> struct dd_events {
+    hipEvent_t ev[N] = {};
+    hipError_t init() {
+        for (auto &e : ev)
+            if (hipError_t r = hipEventCreate(&e)) return r;
+        return hipSuccess;
+    }
+    hipError_t record(int i, hipStream_t s) { return hipEventRecord(ev[i], s); }
+    void elapsed(float *ms, int from, int to) const {
+        (void)hipEventElapsedTime(ms, ev[from], ev[to]);
+    }
+    ~dd_events() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+/* the layout checks of DESIGN.md §18.1; rows_p: rows per partition */
+static dd_status dd_check_layout(const std::string &who, int64_t n, const int64_t *seg_offsets,
+                                 const int32_t *seg_part, int32_t n_segs, int32_t n_parts,
+                                 std::vector<int64_t> *rows_p) {
+    if (n_segs < 1 || n_parts < 1)
+        return set_err(DD_ERR_INVALID, who + "at least one segment and one partition");
+    if (seg_offsets[0] != 0 || seg_offsets[n_segs] != n)
+        return set_err(DD_ERR_INVALID, who + "seg_offsets must run from 0 to n_rows");
+    rows_p->assign((size_t)n_parts, 0);
+    for (int s = 0; s < n_segs; s++) {
+        if (seg_offsets[s + 1] < seg_offsets[s])
+            return set_err(DD_ERR_INVALID, who + "seg_offsets decrease");
+        if (seg_part[s] < 0 || seg_part[s] >= n_parts)
+            return set_err(DD_ERR_INVALID, who + "seg_part outside [0, n_parts)");
+        (*rows_p)[seg_part[s]] += seg_offsets[s + 1] - seg_offsets[s];
+    }
+    return DD_OK;
+}
+
+/* One claim / build table region per partition. A partition of `rows` rows gets
+ * max(64, next_pow2(2 * rows)) slots (finalagg.table_slots is the same arithmetic). */
+struct dd_table_regions {
+    std::vector<uint32_t> base, log2;
+    uint64_t n_slots = 0;
+    /* false: the table would pass 2^32 slots, which the caller refuses in its own words */
+    bool size(const std::vector<int64_t> &rows_p) {
+        base.assign(rows_p.size(), 0);
+        log2.assign(rows_p.size(), 0);
+        n_slots = 0;
+        for (size_t p = 0; p < rows_p.size() && n_slots < ((uint64_t)1 << 32); p++) {
+            uint32_t lg = 6;
+            static_assert((1 << 6) == DD_F_MIN_SLOTS, "smallest region");
+            while (((int64_t)1 << lg) < 2 * rows_p[p]) lg++;
+            log2[p] = lg;
+            base[p] = (uint32_t)n_slots;
+            n_slots += (uint64_t)1 << lg;
+        }
+        return n_slots < ((uint64_t)1 << 32);
+    }
+};
+
+/* a list of columns to gather: indices in range, fixed-width dtypes only */
+static dd_status dd_check_projection(const std::string &who, const dd_batch_desc *b,
+                                     const int32_t *proj, int32_t n_proj) {
+    if (n_proj < 0 || n_proj > DD_MAX_COLS || (n_proj > 0 && !proj))
+        return set_err(DD_ERR_INVALID, who + "projection list out of range");
+    for (int i = 0; i < n_proj; i++) {
+        if (proj[i] < 0 || proj[i] >= b->n_cols)
+            return set_err(DD_ERR_INVALID, who + "projected column index out of range");
+        const dd_col_desc &cd = b->cols[proj[i]];
+        if (cd.dtype == DD_DT_UTF8)
+            return set_err(DD_ERR_UNSUPPORTED,
+                           who + "projection: a var-width (utf8 / utf8view) column is not "
+                                 "supported");
+        if (cd.dtype == DD_DT_DICT32)
+            return set_err(DD_ERR_UNSUPPORTED,
+                           who + "projection: a dict32 column is not supported");
+        if (fixed_elem_size(cd.dtype) == 0)
+            return set_err(DD_ERR_INVALID, who + "projection: unknown dtype");
+        if (cd.dtype == DD_DT_DEC128 && (uintptr_t)cd.data % 16)
+            return set_err(DD_ERR_INVALID, who + "dec128 column data must be 16-byte aligned");
+    }
+    return DD_OK;
+}
+
+/* the typed output columns of a run, owned: dd_joiner, dd_sorter and dd_finalizer embed it */
+struct dd_out_cols {
+    std::vector<void *> data;        /* per column; null only at zero rows */
+    std::vector<uint8_t *> validity; /* null: the column has none */
+    /* a column of n_out rows gathered from cd, added here and to g. always_valid: it
+     * carries validity even where its source has none (a NULL-extended outer-join side) */
+    hipError_t add(const dd_col_desc &cd, int64_t n_out, bool always_valid, dd_join_gather *g) {
+        const int c = g->n_cols++;
+        g->elem[c] = fixed_elem_size(cd.dtype);
+        g->src[c] = cd.data;
+        g->src_valid[c] = (const uint8_t *)cd.validity;
+        data.push_back(nullptr);
+        validity.push_back(nullptr);
+        hipError_t e = hipMalloc(&data.back(), n_out ? (size_t)n_out * g->elem[c] : 1);
+        if (e == hipSuccess && (cd.validity || always_valid))
+            e = hipMalloc((void **)&validity.back(), n_out ? (size_t)n_out : 1);
+        g->dst[c] = data.back();
+        g->dst_valid[c] = validity.back();
+        return e;
+    }
+    const void *data_at(int32_t i) const {
+        return i >= 0 && (size_t)i < data.size() ? data[(size_t)i] : nullptr;
+    }
+    const uint8_t *validity_at(int32_t i) const {
+        return i >= 0 && (size_t)i < validity.size() ? validity[(size_t)i] : nullptr;
+    }
+    void clear() {
+        for (void *p : data) (void)hipFree(p);
+        for (uint8_t *p : validity) (void)hipFree(p);
+        data.clear();
+        validity.clear();
+    }
+    ~dd_out_cols() { clear(); }
+};
+
 /* ---------------- partial aggregation (dd_reducer) ---------------- */
 
 struct dd_reducer {
@@ -2336,20 +2499,7 @@ extern "C" dd_status dd_partial_reduce_run(const dd_batch_desc *batch,
     const bool wide = plan.kernel == 1;
 
     dd_kargs ka;
-    memset(&ka, 0, sizeof(ka));
-    ka.n_rows = n;
-    ka.n_cols = batch->n_cols;
-    ka.n_keys = n_keys;
-    for (int k = 0; k < n_keys; k++) ka.key_idx[k] = key_cols[k];
-    for (int c = 0; c < batch->n_cols; c++) {
-        const dd_col_desc &cd = batch->cols[c];
-        dd_kcol &kc = ka.cols[c];
-        kc.dtype = cd.dtype;
-        kc.elem = fixed_elem_size(cd.dtype);
-        kc.data = cd.data;
-        kc.valid = cd.validity;
-        kc.offsets = cd.offsets;
-    }
+    dd_fill_kargs(batch, key_cols, n_keys, &ka);
 
     const int64_t nblocks = plan.nblocks, chunk = plan.chunk;
     /* spill worst case + table flush */
@@ -2482,46 +2632,13 @@ struct dd_finalizer {
     float kernel_ms[3] = {0, 0, 0}; /* claim, scan, merge */
     /* dd_finalizer_columns: keys, aggregates, then the optional nn columns */
     std::vector<int32_t> col_dtype;
-    std::vector<void *> col_data;
-    std::vector<uint8_t *> col_validity; /* null: the column has none */
-    void free_columns() {
-        for (void *p : col_data) (void)hipFree(p);
-        for (uint8_t *p : col_validity) (void)hipFree(p);
-        col_dtype.clear();
-        col_data.clear();
-        col_validity.clear();
-    }
+    dd_out_cols cols;
     ~dd_finalizer() {
         (void)hipFree(keys);
         (void)hipFree(keynull);
         (void)hipFree(aggs);
         (void)hipFree(hi);
         (void)hipFree(nn);
-        free_columns();
-    }
-};
-
-/* claim-table region of a partition with `rows` rows: max(64, next_pow2(2 * rows)) slots,
- * returned as its log2 (finalagg.table_slots is the same arithmetic) */
-static uint32_t dd_final_region_log2(int64_t rows) {
-    uint32_t lg = 6;
-    static_assert((1 << 6) == DD_F_MIN_SLOTS, "smallest region");
-    while (((int64_t)1 << lg) < 2 * rows) lg++;
-    return lg;
-}
-
-/* frees every device pointer handed to it when it goes out of scope */
-struct dd_dev_scratch {
-    std::vector<void *> ptrs;
-    template <typename T> bool alloc(T **p, size_t bytes) {
-        void *v = nullptr;
-        if (hipMalloc(&v, bytes ? bytes : 1) != hipSuccess) return false;
-        ptrs.push_back(v);
-        *p = (T *)v;
-        return true;
-    }
-    ~dd_dev_scratch() {
-        for (void *p : ptrs) (void)hipFree(p);
     }
 };
 
@@ -2602,33 +2719,14 @@ extern "C" dd_status dd_final_merge_run(const dd_batch_desc *batch, const int32_
         plan.nn_cols[g] = nn_cols[g];
     }
     /* segment layout -> rows per partition -> table regions */
-    if (n_segs < 1 || n_parts < 1)
-        return set_err(DD_ERR_INVALID, "final merge: malformed segment layout: at least one "
-                                       "segment and one partition");
-    if (seg_offsets[0] != 0 || seg_offsets[n_segs] != n)
-        return set_err(DD_ERR_INVALID, "final merge: malformed segment layout: seg_offsets "
-                                       "must run from 0 to n_rows");
-    std::vector<int64_t> rows_p((size_t)n_parts, 0);
-    for (int s = 0; s < n_segs; s++) {
-        if (seg_offsets[s + 1] < seg_offsets[s])
-            return set_err(DD_ERR_INVALID, "final merge: malformed segment layout: "
-                                           "seg_offsets decrease");
-        if (seg_part[s] < 0 || seg_part[s] >= n_parts)
-            return set_err(DD_ERR_INVALID, "final merge: malformed segment layout: seg_part "
-                                           "outside [0, n_parts)");
-        rows_p[seg_part[s]] += seg_offsets[s + 1] - seg_offsets[s];
-    }
-    std::vector<uint32_t> base_h((size_t)n_parts), log2_h((size_t)n_parts);
-    uint64_t n_slots = 0;
-    for (int p = 0; p < n_parts; p++) {
-        log2_h[p] = dd_final_region_log2(rows_p[p]);
-        if (n_slots >= ((uint64_t)1 << 32))
-            break;
-        base_h[p] = (uint32_t)n_slots;
-        n_slots += (uint64_t)1 << log2_h[p];
-    }
-    if (n_slots >= ((uint64_t)1 << 32))
+    std::vector<int64_t> rows_p;
+    if (dd_status st = dd_check_layout("final merge: malformed segment layout: ", n,
+                                       seg_offsets, seg_part, n_segs, n_parts, &rows_p))
+        return st;
+    dd_table_regions reg;
+    if (!reg.size(rows_p))
         return set_err(DD_ERR_UNSUPPORTED, "final merge: claim table past 2^32 slots");
+    const uint64_t n_slots = reg.n_slots;
 
     auto f = std::unique_ptr<dd_finalizer>(new dd_finalizer());
     f->n_keys = n_keys;
@@ -2642,20 +2740,7 @@ extern "C" dd_status dd_final_merge_run(const dd_batch_desc *batch, const int32_
     if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
 
     dd_kargs ka;
-    memset(&ka, 0, sizeof(ka));
-    ka.n_rows = n;
-    ka.n_cols = batch->n_cols;
-    ka.n_keys = n_keys;
-    for (int k = 0; k < n_keys; k++) ka.key_idx[k] = key_cols[k];
-    for (int c = 0; c < batch->n_cols; c++) {
-        const dd_col_desc &cd = batch->cols[c];
-        dd_kcol &kc = ka.cols[c];
-        kc.dtype = cd.dtype;
-        kc.elem = fixed_elem_size(cd.dtype);
-        kc.data = cd.data;
-        kc.valid = cd.validity;
-        kc.offsets = cd.offsets;
-    }
+    dd_fill_kargs(batch, key_cols, n_keys, &ka);
 
     hipStream_t s = (hipStream_t)stream;
     dd_dev_scratch ws;
@@ -2664,41 +2749,28 @@ extern "C" dd_status dd_final_merge_run(const dd_batch_desc *batch, const int32_
     uint32_t *d_base = nullptr, *d_log2 = nullptr, *table = nullptr, *slot_gid = nullptr,
              *row_slot = nullptr, *block_sums = nullptr, *err = nullptr;
     const size_t nb = (size_t)((n_slots + DD_F_SCAN_TILE - 1) / DD_F_SCAN_TILE);
-    if (!ws.alloc(&d_seg_off, ((size_t)n_segs + 1) * 8) ||
-        !ws.alloc(&d_seg_part, (size_t)n_segs * 4) || !ws.alloc(&d_base, (size_t)n_parts * 4) ||
-        !ws.alloc(&d_log2, (size_t)n_parts * 4) || !ws.alloc(&d_goff, ((size_t)n_parts + 1) * 8) ||
+    if (!ws.alloc(&d_goff, ((size_t)n_parts + 1) * 8) ||
         !ws.alloc(&table, (size_t)n_slots * 4) || !ws.alloc(&slot_gid, (size_t)n_slots * 4) ||
         !ws.alloc(&row_slot, (size_t)n * 4) || !ws.alloc(&block_sums, (nb + 1) * 4) ||
         !ws.alloc(&err, 4))
         return set_err(DD_ERR_HIP, "final merge: workspace alloc");
-    hipEvent_t ev[5] = {};
-    struct ev_guard {
-        hipEvent_t *e;
-        ~ev_guard() {
-            for (int i = 0; i < 5; i++)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } evg{ev};
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMemcpyAsync(d_seg_off, seg_offsets, ((size_t)n_segs + 1) * 8,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_seg_part, seg_part, (size_t)n_segs * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_base, base_h.data(), (size_t)n_parts * 4, hipMemcpyHostToDevice,
-                           s));
-    HIP_TRY(hipMemcpyAsync(d_log2, log2_h.data(), (size_t)n_parts * 4, hipMemcpyHostToDevice,
-                           s));
+    dd_events<5> ev;
+    HIP_TRY(ev.init());
+    HIP_TRY(ws.upload(&d_seg_off, seg_offsets, (size_t)n_segs + 1, s));
+    HIP_TRY(ws.upload(&d_seg_part, seg_part, (size_t)n_segs, s));
+    HIP_TRY(ws.upload(&d_base, reg.base.data(), (size_t)n_parts, s));
+    HIP_TRY(ws.upload(&d_log2, reg.log2.data(), (size_t)n_parts, s));
     HIP_TRY(hipMemsetAsync(err, 0, 4, s));
-    /* the host vectors above are pageable: the copies have left them before they die */
-    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(s)); /* the uploads have left their pageable sources */
 
-    HIP_TRY(hipEventRecord(ev[0], s));
+    HIP_TRY(ev.record(0, s));
     HIP_TRY(hipMemsetAsync(table, 0xff, (size_t)n_slots * 4, s)); /* DD_F_EMPTY */
     HIP_TRY(dd_launch_final_claim(&ka, d_seg_off, d_seg_part, n_segs, d_base, d_log2, table,
                                   row_slot, err, s));
-    HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(ev.record(1, s));
     HIP_TRY(dd_launch_final_scan(table, n_slots, block_sums, slot_gid, d_base, n_parts, d_goff,
                                  s));
-    HIP_TRY(hipEventRecord(ev[2], s));
+    HIP_TRY(ev.record(2, s));
     HIP_TRY(hipMemcpyAsync(f->group_offsets.data(), d_goff, ((size_t)n_parts + 1) * 8,
                            hipMemcpyDeviceToHost, s));
     uint32_t err_h = 0;
@@ -2713,14 +2785,14 @@ extern "C" dd_status dd_final_merge_run(const dd_batch_desc *batch, const int32_
     HIP_TRY(hipMalloc((void **)&f->aggs, (size_t)ng * n_aggs * 8));
     HIP_TRY(hipMalloc((void **)&f->hi, (size_t)ng * n_aggs * 8));
     HIP_TRY(hipMalloc((void **)&f->nn, (size_t)ng * n_aggs * 8));
-    HIP_TRY(hipEventRecord(ev[3], s));
+    HIP_TRY(ev.record(3, s));
     HIP_TRY(dd_launch_final_merge(&ka, &plan, table, row_slot, slot_gid, ng, f->keys,
                                   f->keynull, f->aggs, f->hi, f->nn, s));
-    HIP_TRY(hipEventRecord(ev[4], s));
+    HIP_TRY(ev.record(4, s));
     HIP_TRY(hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&f->kernel_ms[0], ev[0], ev[1]);
-    (void)hipEventElapsedTime(&f->kernel_ms[1], ev[1], ev[2]);
-    (void)hipEventElapsedTime(&f->kernel_ms[2], ev[3], ev[4]);
+    ev.elapsed(&f->kernel_ms[0], 0, 1);
+    ev.elapsed(&f->kernel_ms[1], 1, 2);
+    ev.elapsed(&f->kernel_ms[2], 3, 4);
     *out = f.release();
     return DD_OK;
 }
@@ -2794,12 +2866,14 @@ extern "C" dd_status dd_finalizer_columns(dd_finalizer *f, const int32_t *key_dt
             return set_err(DD_ERR_INVALID, "final columns: unknown aggregate op");
         c.ops[j] = agg_ops[j];
     }
-    f->free_columns();
+    std::vector<void *> &col_data = f->cols.data;
+    std::vector<uint8_t *> &col_validity = f->cols.validity;
+    f->cols.clear();
     const int64_t ng = f->n_groups;
     const int n_cols = n_keys + n_aggs * (with_nn ? 2 : 1);
     f->col_dtype.assign((size_t)n_cols, 0);
-    f->col_data.assign((size_t)n_cols, nullptr);
-    f->col_validity.assign((size_t)n_cols, nullptr);
+    col_data.assign((size_t)n_cols, nullptr);
+    col_validity.assign((size_t)n_cols, nullptr);
     for (int i = 0; i < n_cols; i++) {
         int dt = DD_DT_I64; /* count, the i64 aggregates, nn */
         bool has_valid = true;
@@ -2816,16 +2890,16 @@ extern "C" dd_status dd_finalizer_columns(dd_finalizer *f, const int32_t *key_dt
         }
         f->col_dtype[i] = dt;
         if (ng == 0) continue; /* no device work, as the run itself at zero rows */
-        HIP_TRY(hipMalloc(&f->col_data[i], (size_t)ng * fixed_elem_size(dt)));
-        if (has_valid) HIP_TRY(hipMalloc((void **)&f->col_validity[i], (size_t)ng));
+        HIP_TRY(hipMalloc(&col_data[i], (size_t)ng * fixed_elem_size(dt)));
+        if (has_valid) HIP_TRY(hipMalloc((void **)&col_validity[i], (size_t)ng));
         if (i < n_keys) {
-            c.key_data[i] = f->col_data[i];
-            c.key_valid[i] = f->col_validity[i];
+            c.key_data[i] = col_data[i];
+            c.key_valid[i] = col_validity[i];
         } else if (i < n_keys + n_aggs) {
-            c.agg_data[i - n_keys] = f->col_data[i];
-            c.agg_valid[i - n_keys] = f->col_validity[i];
+            c.agg_data[i - n_keys] = col_data[i];
+            c.agg_valid[i - n_keys] = col_validity[i];
         } else {
-            c.nn_data[i - n_keys - n_aggs] = (int64_t *)f->col_data[i];
+            c.nn_data[i - n_keys - n_aggs] = (int64_t *)col_data[i];
         }
     }
     if (ng == 0) return DD_OK;
@@ -2836,7 +2910,7 @@ extern "C" dd_status dd_finalizer_columns(dd_finalizer *f, const int32_t *key_dt
 }
 
 extern "C" int32_t dd_finalizer_n_cols(const dd_finalizer *f) {
-    return f ? (int32_t)f->col_data.size() : 0;
+    return f ? (int32_t)f->cols.data.size() : 0;
 }
 
 extern "C" int32_t dd_finalizer_col_dtype(const dd_finalizer *f, int32_t i) {
@@ -2844,51 +2918,28 @@ extern "C" int32_t dd_finalizer_col_dtype(const dd_finalizer *f, int32_t i) {
 }
 
 extern "C" const void *dd_finalizer_col_data(const dd_finalizer *f, int32_t i) {
-    return f && i >= 0 && i < (int32_t)f->col_data.size() ? f->col_data[i] : nullptr;
+    return f ? f->cols.data_at(i) : nullptr;
 }
 
 extern "C" const uint8_t *dd_finalizer_col_validity(const dd_finalizer *f, int32_t i) {
-    return f && i >= 0 && i < (int32_t)f->col_validity.size() ? f->col_validity[i] : nullptr;
+    return f ? f->cols.validity_at(i) : nullptr;
 }
 
 extern "C" void dd_finalizer_destroy(dd_finalizer *f) { delete f; }
 
-/* ---------------- hash join above two shuffles (dd_joiner) ---------------- */
+/* ---------------- hash join above two shuffles (dd_joiner) ---------- */
 
 struct dd_joiner {
     int64_t n_rows = 0;
-    std::vector<int64_t> seg_offsets; /* [emitting side's n_segs + 1] */
+    std::vector<int64_t> seg_offsets; /* [output segments + 1] */
     uint32_t *build_idx = nullptr, *probe_idx = nullptr;
-    std::vector<void *> col_data;        /* per output column; null only at zero rows */
-    std::vector<uint8_t *> col_validity; /* null when the source has none */
+    dd_out_cols cols;                     /* build_proj's columns, then probe_proj's */
     float kernel_ms[5] = {0, 0, 0, 0, 0}; /* build, count, scan, emit, gather */
     ~dd_joiner() {
         (void)hipFree(build_idx);
         (void)hipFree(probe_idx);
-        for (void *p : col_data) (void)hipFree(p);
-        for (uint8_t *p : col_validity) (void)hipFree(p);
     }
 };
-
-/* §18.1's layout checks for one side; rows_p: rows per partition */
-static dd_status dd_join_check_layout(const char *side, int64_t n, const int64_t *seg_offsets,
-                                      const int32_t *seg_part, int32_t n_segs, int32_t n_parts,
-                                      std::vector<int64_t> *rows_p) {
-    const std::string who = std::string("hash join: malformed ") + side + " segment layout: ";
-    if (n_segs < 1 || n_parts < 1)
-        return set_err(DD_ERR_INVALID, who + "at least one segment and one partition");
-    if (seg_offsets[0] != 0 || seg_offsets[n_segs] != n)
-        return set_err(DD_ERR_INVALID, who + "seg_offsets must run from 0 to n_rows");
-    rows_p->assign((size_t)n_parts, 0);
-    for (int s = 0; s < n_segs; s++) {
-        if (seg_offsets[s + 1] < seg_offsets[s])
-            return set_err(DD_ERR_INVALID, who + "seg_offsets decrease");
-        if (seg_part[s] < 0 || seg_part[s] >= n_parts)
-            return set_err(DD_ERR_INVALID, who + "seg_part outside [0, n_parts)");
-        (*rows_p)[seg_part[s]] += seg_offsets[s + 1] - seg_offsets[s];
-    }
-    return DD_OK;
-}
 
 /* key and projection checks of one side */
 static dd_status dd_join_check_side(const char *side, const dd_batch_desc *b,
@@ -2921,52 +2972,8 @@ static dd_status dd_join_check_side(const char *side, const dd_batch_desc *b,
             return set_err(DD_ERR_INVALID, who + "unknown key dtype");
         }
     }
-    if (n_proj < 0 || n_proj > DD_MAX_COLS || (n_proj > 0 && !proj))
-        return set_err(DD_ERR_INVALID, who + "projection list out of range");
-    for (int i = 0; i < n_proj; i++) {
-        if (proj[i] < 0 || proj[i] >= b->n_cols)
-            return set_err(DD_ERR_INVALID, who + "projected column index out of range");
-        const dd_col_desc &cd = b->cols[proj[i]];
-        if (cd.dtype == DD_DT_UTF8)
-            return set_err(DD_ERR_UNSUPPORTED,
-                           who + "projection: a var-width (utf8 / utf8view) column is not "
-                                 "supported");
-        if (cd.dtype == DD_DT_DICT32)
-            return set_err(DD_ERR_UNSUPPORTED,
-                           who + "projection: a dict32 column is not supported");
-        if (fixed_elem_size(cd.dtype) == 0)
-            return set_err(DD_ERR_INVALID, who + "projection: unknown dtype");
-        if (cd.dtype == DD_DT_DEC128 && (uintptr_t)cd.data % 16)
-            return set_err(DD_ERR_INVALID, who + "dec128 column data must be 16-byte aligned");
-    }
-    return DD_OK;
+    return dd_check_projection(who, b, proj, n_proj);
 }
-
-static void dd_join_kargs(const dd_batch_desc *b, const int32_t *keys, int32_t n_keys,
-                          dd_kargs *ka) {
-    memset(ka, 0, sizeof(*ka));
-    ka->n_rows = b->n_rows;
-    ka->n_cols = b->n_cols;
-    ka->n_keys = n_keys;
-    for (int k = 0; k < n_keys; k++) ka->key_idx[k] = keys[k];
-    for (int c = 0; c < b->n_cols; c++) {
-        const dd_col_desc &cd = b->cols[c];
-        dd_kcol &kc = ka->cols[c];
-        kc.dtype = cd.dtype;
-        kc.elem = fixed_elem_size(cd.dtype);
-        kc.data = cd.data;
-        kc.valid = cd.validity;
-        kc.offsets = cd.offsets;
-    }
-}
-
-/* what dd_hash_join_run and dd_hash_join_outer_run check alike, all before any device
- * work: key count, both sides' keys and projections, both layouts, co-partitioning; and the
- * table regions from the BUILD side's rows per partition (the final merge's sizing) */
-struct dd_join_regions {
-    std::vector<uint32_t> base, log2;
-    uint64_t n_slots = 0;
-};
 
 static dd_status dd_join_check_n_keys(int32_t n_keys) {
     if (n_keys > 4) return set_err(DD_ERR_UNSUPPORTED, "hash join: more than 4 key columns");
@@ -2974,13 +2981,24 @@ static dd_status dd_join_check_n_keys(int32_t n_keys) {
     return DD_OK;
 }
 
-static dd_status dd_join_check_inputs(
-    const dd_batch_desc *build, const int32_t *build_keys, const dd_batch_desc *probe,
-    const int32_t *probe_keys, int32_t n_keys, const int64_t *build_seg_offsets,
-    const int32_t *build_seg_part, int32_t build_n_segs, int32_t build_n_parts,
-    const int64_t *probe_seg_offsets, const int32_t *probe_seg_part, int32_t probe_n_segs,
-    int32_t probe_n_parts, const int32_t *build_proj, int32_t n_build_proj,
-    const int32_t *probe_proj, int32_t n_probe_proj, dd_join_regions *reg) {
+/* The body of dd_hash_join_run and dd_hash_join_outer_run, which have validated join_type
+ * and n_keys. `who` opens the messages the two entries word differently. What a join type
+ * scans and keeps:
+ *   inner, right_semi, right_anti: the probe rows, in the probe side's segments;
+ *   left_semi, left_anti: the build rows, in the build side's segments;
+ *   left, right, full (outer): the probe rows in the probe side's segments; keep_probe: those
+ *   without a match come out with the build side NULL; keep_build: the unmatched build rows
+ *   follow in a second section, the build side's segments, with the probe side NULL. */
+static dd_status dd_join_run(
+    const std::string &who, const dd_batch_desc *build, const int32_t *build_keys,
+    const dd_batch_desc *probe, const int32_t *probe_keys, int32_t n_keys, int32_t join_type,
+    const int64_t *build_seg_offsets, const int32_t *build_seg_part, int32_t build_n_segs,
+    int32_t build_n_parts, const int64_t *probe_seg_offsets, const int32_t *probe_seg_part,
+    int32_t probe_n_segs, int32_t probe_n_parts, const int32_t *build_proj,
+    int32_t n_build_proj, const int32_t *probe_proj, int32_t n_probe_proj, void *stream,
+    dd_joiner **out) {
+    /* all before any device work: both sides' keys and projections, both layouts,
+     * co-partitioning, and the table regions from the BUILD side's rows per partition */
     dd_status st = dd_join_check_side("build side:", build, build_keys, n_keys, build_proj,
                                       n_build_proj);
     if (st != DD_OK) return st;
@@ -2993,26 +3011,159 @@ static dd_status dd_join_check_inputs(
     if (n_build_proj + n_probe_proj > DD_MAX_COLS)
         return set_err(DD_ERR_INVALID, "hash join: more output columns than a batch holds");
     std::vector<int64_t> rows_b, rows_p;
-    st = dd_join_check_layout("build", build->n_rows, build_seg_offsets, build_seg_part,
-                              build_n_segs, build_n_parts, &rows_b);
+    st = dd_check_layout("hash join: malformed build segment layout: ", build->n_rows,
+                         build_seg_offsets, build_seg_part, build_n_segs, build_n_parts, &rows_b);
     if (st != DD_OK) return st;
-    st = dd_join_check_layout("probe", probe->n_rows, probe_seg_offsets, probe_seg_part,
-                              probe_n_segs, probe_n_parts, &rows_p);
+    st = dd_check_layout("hash join: malformed probe segment layout: ", probe->n_rows,
+                         probe_seg_offsets, probe_seg_part, probe_n_segs, probe_n_parts, &rows_p);
     if (st != DD_OK) return st;
     if (build_n_parts != probe_n_parts)
         return set_err(DD_ERR_INVALID, "hash join: unequal n_parts: the two sides must be "
                                        "co-partitioned");
     const int32_t n_parts = build_n_parts;
-    reg->base.assign((size_t)n_parts, 0);
-    reg->log2.assign((size_t)n_parts, 0);
-    reg->n_slots = 0;
-    for (int p = 0; p < n_parts && reg->n_slots < ((uint64_t)1 << 32); p++) {
-        reg->log2[p] = dd_final_region_log2(rows_b[p]);
-        reg->base[p] = (uint32_t)reg->n_slots;
-        reg->n_slots += (uint64_t)1 << reg->log2[p];
-    }
-    if (reg->n_slots >= ((uint64_t)1 << 32))
+    dd_table_regions reg;
+    if (!reg.size(rows_b))
         return set_err(DD_ERR_UNSUPPORTED, "hash join: build table past 2^32 slots");
+
+    const bool outer = join_type >= DD_JOIN_LEFT;
+    const bool left = join_type == DD_JOIN_LEFT_SEMI || join_type == DD_JOIN_LEFT_ANTI;
+    const bool right = join_type == DD_JOIN_RIGHT_SEMI || join_type == DD_JOIN_RIGHT_ANTI;
+    const bool anti = join_type == DD_JOIN_LEFT_ANTI || join_type == DD_JOIN_RIGHT_ANTI;
+    const bool keep_probe = outer && join_type != DD_JOIN_LEFT;
+    const bool keep_build = outer && join_type != DD_JOIN_RIGHT;
+    const int64_t nb_rows = build->n_rows, np_rows = probe->n_rows;
+    const int64_t n_tail = keep_build ? nb_rows : 0;
+    const int64_t n_scan = left ? nb_rows : np_rows + n_tail; /* < 2^32 */
+    const int32_t o_n_segs = left ? build_n_segs : probe_n_segs + (keep_build ? build_n_segs : 0);
+
+    auto j = std::unique_ptr<dd_joiner>(new dd_joiner());
+    j->seg_offsets.assign((size_t)o_n_segs + 1, 0);
+    if (n_scan == 0) { /* nothing can come out: zero rows, no device work */
+        *out = j.release();
+        return DD_OK;
+    }
+    if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
+
+    /* an outer join's scan boundaries over cnt[np_rows + n_tail]: the probe segments, then
+     * the build segments shifted behind the probe rows */
+    std::vector<int64_t> oseg_h;
+    if (outer) {
+        oseg_h.assign(probe_seg_offsets, probe_seg_offsets + probe_n_segs + 1);
+        if (keep_build)
+            for (int s = 1; s <= build_n_segs; s++)
+                oseg_h.push_back(np_rows + build_seg_offsets[s]);
+    }
+
+    dd_kargs kb, kp;
+    dd_fill_kargs(build, build_keys, n_keys, &kb);
+    dd_fill_kargs(probe, probe_keys, n_keys, &kp);
+
+    hipStream_t s = (hipStream_t)stream;
+    dd_dev_scratch ws;
+    int64_t *d_bseg_off = nullptr, *d_pseg_off = nullptr, *d_oseg_off = nullptr,
+            *d_seg_out = nullptr;
+    int32_t *d_bseg_part = nullptr, *d_pseg_part = nullptr;
+    uint32_t *d_base = nullptr, *d_log2 = nullptr, *table = nullptr, *next = nullptr,
+             *cnt = nullptr, *head = nullptr, *err = nullptr;
+    uint64_t *sums = nullptr;
+    uint8_t *matched = nullptr; /* per build row, where build rows are emitted */
+    const size_t n_pad = ((size_t)n_scan + 3) & ~(size_t)3;
+    const size_t nb = (n_pad + DD_J_SCAN_TILE - 1) / DD_J_SCAN_TILE;
+    if (!ws.alloc(&d_seg_out, ((size_t)o_n_segs + 2) * 8) ||
+        !ws.alloc(&table, (size_t)reg.n_slots * 4) || !ws.alloc(&next, (size_t)nb_rows * 4) ||
+        !ws.alloc(&cnt, n_pad * 4) || (outer && !ws.alloc(&head, (size_t)np_rows * 4)) ||
+        !ws.alloc(&sums, (nb + 1) * 8) || !ws.alloc(&err, 4) ||
+        ((left || keep_build) && !ws.alloc(&matched, (size_t)nb_rows)))
+        return set_err(DD_ERR_HIP, who + "workspace alloc");
+    dd_events<7> ev;
+    HIP_TRY(ev.init());
+    HIP_TRY(ws.upload(&d_bseg_off, build_seg_offsets, (size_t)build_n_segs + 1, s));
+    HIP_TRY(ws.upload(&d_bseg_part, build_seg_part, (size_t)build_n_segs, s));
+    HIP_TRY(ws.upload(&d_pseg_off, probe_seg_offsets, (size_t)probe_n_segs + 1, s));
+    HIP_TRY(ws.upload(&d_pseg_part, probe_seg_part, (size_t)probe_n_segs, s));
+    if (outer) HIP_TRY(ws.upload(&d_oseg_off, oseg_h.data(), oseg_h.size(), s));
+    HIP_TRY(ws.upload(&d_base, reg.base.data(), (size_t)n_parts, s));
+    HIP_TRY(ws.upload(&d_log2, reg.log2.data(), (size_t)n_parts, s));
+    HIP_TRY(hipMemsetAsync(err, 0, 4, s));
+    HIP_TRY(hipStreamSynchronize(s)); /* the uploads have left their pageable sources */
+    const int64_t *d_scan_off = outer ? d_oseg_off : left ? d_bseg_off : d_pseg_off;
+
+    HIP_TRY(ev.record(0, s));
+    HIP_TRY(hipMemsetAsync(table, 0xff, (size_t)reg.n_slots * 4, s)); /* DD_F_EMPTY */
+    if (nb_rows) HIP_TRY(hipMemsetAsync(next, 0xff, (size_t)nb_rows * 4, s));
+    HIP_TRY(dd_launch_join_build(&kb, d_bseg_off, d_bseg_part, build_n_segs, d_base, d_log2,
+                                 table, next, err, s));
+    HIP_TRY(ev.record(1, s));
+    HIP_TRY(hipMemsetAsync(cnt, 0, n_pad * 4, s));
+    if (matched && nb_rows) HIP_TRY(hipMemsetAsync(matched, 0, (size_t)nb_rows, s));
+    if (outer)
+        HIP_TRY(dd_launch_join_count_outer(&kb, &kp, d_pseg_off, d_pseg_part, probe_n_segs,
+                                           d_base, d_log2, table, next, keep_probe, head, cnt,
+                                           matched, s));
+    else
+        HIP_TRY(dd_launch_join_count(&kb, &kp, d_pseg_off, d_pseg_part, probe_n_segs, d_base,
+                                     d_log2, table, next, join_type, cnt, matched, s));
+    if (left) HIP_TRY(dd_launch_join_left_cnt(matched, nb_rows, anti, cnt, s));
+    if (keep_build) HIP_TRY(dd_launch_join_build_cnt_outer(matched, nb_rows, np_rows, cnt, s));
+    HIP_TRY(ev.record(2, s));
+    HIP_TRY(dd_launch_join_scan(cnt, n_scan, sums, d_scan_off, o_n_segs, d_seg_out, s));
+    HIP_TRY(ev.record(3, s));
+    /* the one mid-run sync: the output is sized by the result */
+    std::vector<int64_t> seg_out_h((size_t)o_n_segs + 2);
+    uint32_t err_h = 0;
+    HIP_TRY(hipMemcpyAsync(seg_out_h.data(), d_seg_out, ((size_t)o_n_segs + 2) * 8,
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&err_h, err, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err_h) return set_err(DD_ERR_HIP, who + "build table overflow (internal)");
+    const uint64_t total = (uint64_t)seg_out_h[(size_t)o_n_segs + 1];
+    if (total >= ((uint64_t)1 << 31))
+        return set_err(DD_ERR_UNSUPPORTED, who + "output of " + std::to_string(total) +
+                                               " rows is 2^31 or more: chunk the probe side");
+    const int64_t n_out = (int64_t)total;
+    j->n_rows = n_out;
+    memcpy(j->seg_offsets.data(), seg_out_h.data(), ((size_t)o_n_segs + 1) * 8);
+
+    const size_t idx_bytes = n_out ? (size_t)n_out * 4 : 1;
+    if (!right) HIP_TRY(hipMalloc((void **)&j->build_idx, idx_bytes));
+    if (!left) HIP_TRY(hipMalloc((void **)&j->probe_idx, idx_bytes));
+    dd_join_gather gb, gp;
+    memset(&gb, 0, sizeof(gb));
+    memset(&gp, 0, sizeof(gp));
+    /* a NULL-extended side (build when probe rows are kept, probe when build rows are)
+     * always carries validity */
+    for (int i = 0; i < n_build_proj; i++)
+        HIP_TRY(j->cols.add(build->cols[build_proj[i]], n_out, keep_probe, &gb));
+    for (int i = 0; i < n_probe_proj; i++)
+        HIP_TRY(j->cols.add(probe->cols[probe_proj[i]], n_out, keep_build, &gp));
+    HIP_TRY(ev.record(4, s));
+    /* every index is written by the emit; preset first so that no gather ever reads an index
+     * this run did not produce: to 0, or for an outer join to DD_JOIN_NONE, which its gather
+     * never follows */
+    if (j->build_idx) HIP_TRY(hipMemsetAsync(j->build_idx, outer ? 0xff : 0, idx_bytes, s));
+    if (j->probe_idx) HIP_TRY(hipMemsetAsync(j->probe_idx, outer ? 0xff : 0, idx_bytes, s));
+    if (outer)
+        HIP_TRY(dd_launch_join_emit_outer(head, next, matched, cnt, np_rows, n_tail, keep_probe,
+                                          (uint32_t)n_out, j->build_idx, j->probe_idx, s));
+    else if (left)
+        HIP_TRY(dd_launch_join_emit_build(matched, nb_rows, anti, cnt, (uint32_t)n_out,
+                                          j->build_idx, s));
+    else
+        HIP_TRY(dd_launch_join_emit_probe(&kb, &kp, d_pseg_off, d_pseg_part, probe_n_segs,
+                                          d_base, d_log2, table, next, join_type, cnt,
+                                          (uint32_t)n_out, j->build_idx, j->probe_idx, s));
+    HIP_TRY(ev.record(5, s));
+    auto gather = outer ? dd_launch_join_gather_outer : dd_launch_join_gather;
+    HIP_TRY(gather(&gb, j->build_idx, n_out, s));
+    HIP_TRY(gather(&gp, j->probe_idx, n_out, s));
+    HIP_TRY(ev.record(6, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ev.elapsed(&j->kernel_ms[0], 0, 1);
+    ev.elapsed(&j->kernel_ms[1], 1, 2);
+    ev.elapsed(&j->kernel_ms[2], 2, 3);
+    ev.elapsed(&j->kernel_ms[3], 4, 5);
+    ev.elapsed(&j->kernel_ms[4], 5, 6);
+    *out = j.release();
     return DD_OK;
 }
 
@@ -3036,170 +3187,19 @@ extern "C" dd_status dd_hash_join_run(
     if (st != DD_OK) return st;
     const bool left = join_type == DD_JOIN_LEFT_SEMI || join_type == DD_JOIN_LEFT_ANTI;
     const bool right = join_type == DD_JOIN_RIGHT_SEMI || join_type == DD_JOIN_RIGHT_ANTI;
-    const bool anti = join_type == DD_JOIN_LEFT_ANTI || join_type == DD_JOIN_RIGHT_ANTI;
     if (left && n_probe_proj != 0)
         return set_err(DD_ERR_INVALID, "hash join: a left_semi / left_anti join emits build "
                                        "rows: a probe-side projection list is not allowed");
     if (right && n_build_proj != 0)
         return set_err(DD_ERR_INVALID, "hash join: a right_semi / right_anti join emits probe "
                                        "rows: a build-side projection list is not allowed");
-    dd_join_regions reg;
-    st = dd_join_check_inputs(build, build_keys, probe, probe_keys, n_keys, build_seg_offsets,
-                              build_seg_part, build_n_segs, build_n_parts, probe_seg_offsets,
-                              probe_seg_part, probe_n_segs, probe_n_parts, build_proj,
-                              n_build_proj, probe_proj, n_probe_proj, &reg);
-    if (st != DD_OK) return st;
-    const int32_t n_parts = build_n_parts;
-    const std::vector<uint32_t> &base_h = reg.base, &log2_h = reg.log2;
-    const uint64_t n_slots = reg.n_slots;
-
-    const int64_t nb_rows = build->n_rows, np_rows = probe->n_rows;
-    /* the emitting side: its rows are scanned, its segments are kept */
-    const int64_t n_emit = left ? nb_rows : np_rows;
-    const int64_t *e_seg_offsets = left ? build_seg_offsets : probe_seg_offsets;
-    const int32_t e_n_segs = left ? build_n_segs : probe_n_segs;
-    const int n_out_cols = n_build_proj + n_probe_proj;
-
-    auto j = std::unique_ptr<dd_joiner>(new dd_joiner());
-    j->seg_offsets.assign((size_t)e_n_segs + 1, 0);
-    j->col_data.assign((size_t)n_out_cols, nullptr);
-    j->col_validity.assign((size_t)n_out_cols, nullptr);
-    if (n_emit == 0) { /* zero rows, no device work */
-        *out = j.release();
-        return DD_OK;
-    }
-    if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
-
-    dd_kargs kb, kp;
-    dd_join_kargs(build, build_keys, n_keys, &kb);
-    dd_join_kargs(probe, probe_keys, n_keys, &kp);
-
-    hipStream_t s = (hipStream_t)stream;
-    dd_dev_scratch ws;
-    int64_t *d_bseg_off = nullptr, *d_pseg_off = nullptr, *d_seg_out = nullptr;
-    int32_t *d_bseg_part = nullptr, *d_pseg_part = nullptr;
-    uint32_t *d_base = nullptr, *d_log2 = nullptr, *table = nullptr, *next = nullptr,
-             *cnt = nullptr, *err = nullptr;
-    uint64_t *sums = nullptr;
-    uint8_t *matched = nullptr;
-    const size_t n_pad = ((size_t)n_emit + 3) & ~(size_t)3;
-    const size_t nb = (n_pad + DD_J_SCAN_TILE - 1) / DD_J_SCAN_TILE;
-    if (!ws.alloc(&d_bseg_off, ((size_t)build_n_segs + 1) * 8) ||
-        !ws.alloc(&d_bseg_part, (size_t)build_n_segs * 4) ||
-        !ws.alloc(&d_pseg_off, ((size_t)probe_n_segs + 1) * 8) ||
-        !ws.alloc(&d_pseg_part, (size_t)probe_n_segs * 4) ||
-        !ws.alloc(&d_seg_out, ((size_t)e_n_segs + 2) * 8) ||
-        !ws.alloc(&d_base, (size_t)n_parts * 4) || !ws.alloc(&d_log2, (size_t)n_parts * 4) ||
-        !ws.alloc(&table, (size_t)n_slots * 4) || !ws.alloc(&next, (size_t)nb_rows * 4) ||
-        !ws.alloc(&cnt, n_pad * 4) || !ws.alloc(&sums, (nb + 1) * 8) || !ws.alloc(&err, 4) ||
-        (left && !ws.alloc(&matched, (size_t)nb_rows)))
-        return set_err(DD_ERR_HIP, "hash join: workspace alloc");
-    hipEvent_t ev[7] = {};
-    struct ev_guard {
-        hipEvent_t *e;
-        ~ev_guard() {
-            for (int i = 0; i < 7; i++)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } evg{ev};
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMemcpyAsync(d_bseg_off, build_seg_offsets, ((size_t)build_n_segs + 1) * 8,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_bseg_part, build_seg_part, (size_t)build_n_segs * 4,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_pseg_off, probe_seg_offsets, ((size_t)probe_n_segs + 1) * 8,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_pseg_part, probe_seg_part, (size_t)probe_n_segs * 4,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_base, base_h.data(), (size_t)n_parts * 4, hipMemcpyHostToDevice,
-                           s));
-    HIP_TRY(hipMemcpyAsync(d_log2, log2_h.data(), (size_t)n_parts * 4, hipMemcpyHostToDevice,
-                           s));
-    HIP_TRY(hipMemsetAsync(err, 0, 4, s));
-    /* pageable host sources: the copies have left them before anything else happens */
-    HIP_TRY(hipStreamSynchronize(s));
-    const int64_t *d_eseg_off = left ? d_bseg_off : d_pseg_off;
-
-    HIP_TRY(hipEventRecord(ev[0], s));
-    HIP_TRY(hipMemsetAsync(table, 0xff, (size_t)n_slots * 4, s)); /* DD_F_EMPTY */
-    if (nb_rows) HIP_TRY(hipMemsetAsync(next, 0xff, (size_t)nb_rows * 4, s));
-    HIP_TRY(dd_launch_join_build(&kb, d_bseg_off, d_bseg_part, build_n_segs, d_base, d_log2,
-                                 table, next, err, s));
-    HIP_TRY(hipEventRecord(ev[1], s));
-    HIP_TRY(hipMemsetAsync(cnt, 0, n_pad * 4, s));
-    if (left) HIP_TRY(hipMemsetAsync(matched, 0, (size_t)nb_rows, s));
-    HIP_TRY(dd_launch_join_count(&kb, &kp, d_pseg_off, d_pseg_part, probe_n_segs, d_base,
-                                 d_log2, table, next, join_type, cnt, matched, s));
-    if (left) HIP_TRY(dd_launch_join_left_cnt(matched, nb_rows, anti, cnt, s));
-    HIP_TRY(hipEventRecord(ev[2], s));
-    HIP_TRY(dd_launch_join_scan(cnt, n_emit, sums, d_eseg_off, e_n_segs, d_seg_out, s));
-    HIP_TRY(hipEventRecord(ev[3], s));
-    /* the one mid-run sync: the output is sized by the result */
-    std::vector<int64_t> seg_out_h((size_t)e_n_segs + 2);
-    uint32_t err_h = 0;
-    HIP_TRY(hipMemcpyAsync(seg_out_h.data(), d_seg_out, ((size_t)e_n_segs + 2) * 8,
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&err_h, err, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (err_h) return set_err(DD_ERR_HIP, "hash join: build table overflow (internal)");
-    const uint64_t total = (uint64_t)seg_out_h[(size_t)e_n_segs + 1];
-    if (total >= ((uint64_t)1 << 31))
-        return set_err(DD_ERR_UNSUPPORTED, "hash join: output of " + std::to_string(total) +
-                                               " rows is 2^31 or more: chunk the probe side");
-    const int64_t n_out = (int64_t)total;
-    j->n_rows = n_out;
-    memcpy(j->seg_offsets.data(), seg_out_h.data(), ((size_t)e_n_segs + 1) * 8);
-
-    const size_t idx_bytes = n_out ? (size_t)n_out * 4 : 1;
-    if (!right) HIP_TRY(hipMalloc((void **)&j->build_idx, idx_bytes));
-    if (!left) HIP_TRY(hipMalloc((void **)&j->probe_idx, idx_bytes));
-    dd_join_gather gb, gp;
-    memset(&gb, 0, sizeof(gb));
-    memset(&gp, 0, sizeof(gp));
-    for (int i = 0; i < n_out_cols; i++) {
-        const bool from_build = i < n_build_proj;
-        const dd_col_desc &cd = from_build ? build->cols[build_proj[i]]
-                                           : probe->cols[probe_proj[i - n_build_proj]];
-        dd_join_gather &g = from_build ? gb : gp;
-        const int c = g.n_cols++;
-        g.elem[c] = fixed_elem_size(cd.dtype);
-        g.src[c] = cd.data;
-        g.src_valid[c] = (const uint8_t *)cd.validity;
-        HIP_TRY(hipMalloc(&j->col_data[i], n_out ? (size_t)n_out * g.elem[c] : 1));
-        g.dst[c] = j->col_data[i];
-        if (cd.validity) {
-            HIP_TRY(hipMalloc((void **)&j->col_validity[i], n_out ? (size_t)n_out : 1));
-            g.dst_valid[c] = j->col_validity[i];
-        }
-    }
-    HIP_TRY(hipEventRecord(ev[4], s));
-    /* every index is written by the emit; zeroed first so that no gather ever reads an
-     * index this run did not produce */
-    if (j->build_idx) HIP_TRY(hipMemsetAsync(j->build_idx, 0, idx_bytes, s));
-    if (j->probe_idx) HIP_TRY(hipMemsetAsync(j->probe_idx, 0, idx_bytes, s));
-    if (left)
-        HIP_TRY(dd_launch_join_emit_build(matched, nb_rows, anti, cnt, (uint32_t)n_out,
-                                          j->build_idx, s));
-    else
-        HIP_TRY(dd_launch_join_emit_probe(&kb, &kp, d_pseg_off, d_pseg_part, probe_n_segs,
-                                          d_base, d_log2, table, next, join_type, cnt,
-                                          (uint32_t)n_out, j->build_idx, j->probe_idx, s));
-    HIP_TRY(hipEventRecord(ev[5], s));
-    HIP_TRY(dd_launch_join_gather(&gb, j->build_idx, n_out, s));
-    HIP_TRY(dd_launch_join_gather(&gp, j->probe_idx, n_out, s));
-    HIP_TRY(hipEventRecord(ev[6], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&j->kernel_ms[0], ev[0], ev[1]);
-    (void)hipEventElapsedTime(&j->kernel_ms[1], ev[1], ev[2]);
-    (void)hipEventElapsedTime(&j->kernel_ms[2], ev[2], ev[3]);
-    (void)hipEventElapsedTime(&j->kernel_ms[3], ev[4], ev[5]);
-    (void)hipEventElapsedTime(&j->kernel_ms[4], ev[5], ev[6]);
-    *out = j.release();
-    return DD_OK;
+    return dd_join_run("hash join: ", build, build_keys, probe, probe_keys, n_keys, join_type,
+                       build_seg_offsets, build_seg_part, build_n_segs, build_n_parts,
+                       probe_seg_offsets, probe_seg_part, probe_n_segs, probe_n_parts,
+                       build_proj, n_build_proj, probe_proj, n_probe_proj, stream, out);
 }
 
-/* ---------------- outer joins: left, right, full ---------------- */
-
+/* outer joins: left, right, full */
 extern "C" dd_status dd_hash_join_outer_run(
     const dd_batch_desc *build, const int32_t *build_keys, const dd_batch_desc *probe,
     const int32_t *probe_keys, int32_t n_keys, int32_t join_type,
@@ -3219,169 +3219,10 @@ extern "C" dd_status dd_hash_join_outer_run(
                                        "full");
     dd_status st = dd_join_check_n_keys(n_keys);
     if (st != DD_OK) return st;
-    dd_join_regions reg;
-    st = dd_join_check_inputs(build, build_keys, probe, probe_keys, n_keys, build_seg_offsets,
-                              build_seg_part, build_n_segs, build_n_parts, probe_seg_offsets,
-                              probe_seg_part, probe_n_segs, probe_n_parts, build_proj,
-                              n_build_proj, probe_proj, n_probe_proj, &reg);
-    if (st != DD_OK) return st;
-    const int32_t n_parts = build_n_parts;
-    /* keep_probe: probe rows without a match come out with the build side NULL; keep_build:
-     * the unmatched build rows follow in a second section with the probe side NULL */
-    const bool keep_probe = join_type != DD_JOIN_LEFT, keep_build = join_type != DD_JOIN_RIGHT;
-    const int64_t nb_rows = build->n_rows, np_rows = probe->n_rows;
-    const int64_t n_tail = keep_build ? nb_rows : 0;
-    const int64_t n_scan = np_rows + n_tail; /* < 2^32 */
-    const int32_t o_n_segs = probe_n_segs + (keep_build ? build_n_segs : 0);
-    const int n_out_cols = n_build_proj + n_probe_proj;
-
-    auto j = std::unique_ptr<dd_joiner>(new dd_joiner());
-    j->seg_offsets.assign((size_t)o_n_segs + 1, 0);
-    j->col_data.assign((size_t)n_out_cols, nullptr);
-    j->col_validity.assign((size_t)n_out_cols, nullptr);
-    /* nothing can come out: a right join without probe rows, any join of two empty sides */
-    if (n_scan == 0) {
-        *out = j.release();
-        return DD_OK;
-    }
-    if (dd_device_count() == 0) return set_err(DD_ERR_NO_DEVICE, "no HIP device");
-
-    /* the scan's boundaries over cnt[np_rows + n_tail]: the probe segments, then the build
-     * segments shifted behind the probe rows */
-    std::vector<int64_t> oseg_h((size_t)o_n_segs + 1);
-    for (int s = 0; s <= probe_n_segs; s++) oseg_h[(size_t)s] = probe_seg_offsets[s];
-    if (keep_build)
-        for (int s = 1; s <= build_n_segs; s++)
-            oseg_h[(size_t)probe_n_segs + s] = np_rows + build_seg_offsets[s];
-
-    dd_kargs kb, kp;
-    dd_join_kargs(build, build_keys, n_keys, &kb);
-    dd_join_kargs(probe, probe_keys, n_keys, &kp);
-
-    hipStream_t s = (hipStream_t)stream;
-    dd_dev_scratch ws;
-    int64_t *d_bseg_off = nullptr, *d_pseg_off = nullptr, *d_oseg_off = nullptr,
-            *d_seg_out = nullptr;
-    int32_t *d_bseg_part = nullptr, *d_pseg_part = nullptr;
-    uint32_t *d_base = nullptr, *d_log2 = nullptr, *table = nullptr, *next = nullptr,
-             *cnt = nullptr, *head = nullptr, *err = nullptr;
-    uint64_t *sums = nullptr;
-    uint8_t *matched = nullptr;
-    const size_t n_pad = ((size_t)n_scan + 3) & ~(size_t)3;
-    const size_t nb = (n_pad + DD_J_SCAN_TILE - 1) / DD_J_SCAN_TILE;
-    if (!ws.alloc(&d_bseg_off, ((size_t)build_n_segs + 1) * 8) ||
-        !ws.alloc(&d_bseg_part, (size_t)build_n_segs * 4) ||
-        !ws.alloc(&d_pseg_off, ((size_t)probe_n_segs + 1) * 8) ||
-        !ws.alloc(&d_pseg_part, (size_t)probe_n_segs * 4) ||
-        !ws.alloc(&d_oseg_off, ((size_t)o_n_segs + 1) * 8) ||
-        !ws.alloc(&d_seg_out, ((size_t)o_n_segs + 2) * 8) ||
-        !ws.alloc(&d_base, (size_t)n_parts * 4) || !ws.alloc(&d_log2, (size_t)n_parts * 4) ||
-        !ws.alloc(&table, (size_t)reg.n_slots * 4) || !ws.alloc(&next, (size_t)nb_rows * 4) ||
-        !ws.alloc(&cnt, n_pad * 4) || !ws.alloc(&head, (size_t)np_rows * 4) ||
-        !ws.alloc(&sums, (nb + 1) * 8) || !ws.alloc(&err, 4) ||
-        (keep_build && !ws.alloc(&matched, (size_t)nb_rows)))
-        return set_err(DD_ERR_HIP, "outer join: workspace alloc");
-    hipEvent_t ev[7] = {};
-    struct ev_guard {
-        hipEvent_t *e;
-        ~ev_guard() {
-            for (int i = 0; i < 7; i++)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } evg{ev};
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMemcpyAsync(d_bseg_off, build_seg_offsets, ((size_t)build_n_segs + 1) * 8,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_bseg_part, build_seg_part, (size_t)build_n_segs * 4,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_pseg_off, probe_seg_offsets, ((size_t)probe_n_segs + 1) * 8,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_pseg_part, probe_seg_part, (size_t)probe_n_segs * 4,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_oseg_off, oseg_h.data(), ((size_t)o_n_segs + 1) * 8,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_base, reg.base.data(), (size_t)n_parts * 4,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_log2, reg.log2.data(), (size_t)n_parts * 4,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(err, 0, 4, s));
-    /* pageable host sources: the copies have left them before anything else happens */
-    HIP_TRY(hipStreamSynchronize(s));
-
-    HIP_TRY(hipEventRecord(ev[0], s));
-    HIP_TRY(hipMemsetAsync(table, 0xff, (size_t)reg.n_slots * 4, s)); /* DD_F_EMPTY */
-    if (nb_rows) HIP_TRY(hipMemsetAsync(next, 0xff, (size_t)nb_rows * 4, s));
-    HIP_TRY(dd_launch_join_build(&kb, d_bseg_off, d_bseg_part, build_n_segs, d_base, d_log2,
-                                 table, next, err, s));
-    HIP_TRY(hipEventRecord(ev[1], s));
-    HIP_TRY(hipMemsetAsync(cnt, 0, n_pad * 4, s));
-    if (keep_build && nb_rows) HIP_TRY(hipMemsetAsync(matched, 0, (size_t)nb_rows, s));
-    HIP_TRY(dd_launch_join_count_outer(&kb, &kp, d_pseg_off, d_pseg_part, probe_n_segs, d_base,
-                                       d_log2, table, next, keep_probe, head, cnt, matched,
-                                       s));
-    if (keep_build) HIP_TRY(dd_launch_join_build_cnt_outer(matched, nb_rows, np_rows, cnt, s));
-    HIP_TRY(hipEventRecord(ev[2], s));
-    HIP_TRY(dd_launch_join_scan(cnt, n_scan, sums, d_oseg_off, o_n_segs, d_seg_out, s));
-    HIP_TRY(hipEventRecord(ev[3], s));
-    /* the one mid-run sync: the output is sized by the result */
-    std::vector<int64_t> seg_out_h((size_t)o_n_segs + 2);
-    uint32_t err_h = 0;
-    HIP_TRY(hipMemcpyAsync(seg_out_h.data(), d_seg_out, ((size_t)o_n_segs + 2) * 8,
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&err_h, err, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (err_h) return set_err(DD_ERR_HIP, "outer join: build table overflow (internal)");
-    const uint64_t total = (uint64_t)seg_out_h[(size_t)o_n_segs + 1];
-    if (total >= ((uint64_t)1 << 31))
-        return set_err(DD_ERR_UNSUPPORTED, "outer join: output of " + std::to_string(total) +
-                                               " rows is 2^31 or more: chunk the probe side");
-    const int64_t n_out = (int64_t)total;
-    j->n_rows = n_out;
-    memcpy(j->seg_offsets.data(), seg_out_h.data(), ((size_t)o_n_segs + 1) * 8);
-
-    const size_t idx_bytes = n_out ? (size_t)n_out * 4 : 1;
-    HIP_TRY(hipMalloc((void **)&j->build_idx, idx_bytes));
-    HIP_TRY(hipMalloc((void **)&j->probe_idx, idx_bytes));
-    dd_join_gather gb, gp;
-    memset(&gb, 0, sizeof(gb));
-    memset(&gp, 0, sizeof(gp));
-    for (int i = 0; i < n_out_cols; i++) {
-        const bool from_build = i < n_build_proj;
-        const dd_col_desc &cd = from_build ? build->cols[build_proj[i]]
-                                           : probe->cols[probe_proj[i - n_build_proj]];
-        dd_join_gather &g = from_build ? gb : gp;
-        const int c = g.n_cols++;
-        g.elem[c] = fixed_elem_size(cd.dtype);
-        g.src[c] = cd.data;
-        g.src_valid[c] = (const uint8_t *)cd.validity;
-        HIP_TRY(hipMalloc(&j->col_data[i], n_out ? (size_t)n_out * g.elem[c] : 1));
-        g.dst[c] = j->col_data[i];
-        /* a NULL-extended side (build when probe rows are kept, probe when build rows are)
-         * always carries validity */
-        if (cd.validity || (from_build ? keep_probe : keep_build)) {
-            HIP_TRY(hipMalloc((void **)&j->col_validity[i], n_out ? (size_t)n_out : 1));
-            g.dst_valid[c] = j->col_validity[i];
-        }
-    }
-    HIP_TRY(hipEventRecord(ev[4], s));
-    /* every index is written by the emit; preset to DD_JOIN_NONE first, which the gather
-     * never follows, so that no gather reads an index this run did not produce */
-    HIP_TRY(hipMemsetAsync(j->build_idx, 0xff, idx_bytes, s));
-    HIP_TRY(hipMemsetAsync(j->probe_idx, 0xff, idx_bytes, s));
-    HIP_TRY(dd_launch_join_emit_outer(head, next, matched, cnt, np_rows, n_tail, keep_probe,
-                                      (uint32_t)n_out, j->build_idx, j->probe_idx, s));
-    HIP_TRY(hipEventRecord(ev[5], s));
-    HIP_TRY(dd_launch_join_gather_outer(&gb, j->build_idx, n_out, s));
-    HIP_TRY(dd_launch_join_gather_outer(&gp, j->probe_idx, n_out, s));
-    HIP_TRY(hipEventRecord(ev[6], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&j->kernel_ms[0], ev[0], ev[1]);
-    (void)hipEventElapsedTime(&j->kernel_ms[1], ev[1], ev[2]);
-    (void)hipEventElapsedTime(&j->kernel_ms[2], ev[2], ev[3]);
-    (void)hipEventElapsedTime(&j->kernel_ms[3], ev[4], ev[5]);
-    (void)hipEventElapsedTime(&j->kernel_ms[4], ev[5], ev[6]);
-    *out = j.release();
-    return DD_OK;
+    return dd_join_run("outer join: ", build, build_keys, probe, probe_keys, n_keys, join_type,
+                       build_seg_offsets, build_seg_part, build_n_segs, build_n_parts,
+                       probe_seg_offsets, probe_seg_part, probe_n_segs, probe_n_parts,
+                       build_proj, n_build_proj, probe_proj, n_probe_proj, stream, out);
 }
 
 extern "C" int64_t dd_joiner_n_rows(const dd_joiner *j) { return j ? j->n_rows : 0; }
@@ -3400,12 +3241,11 @@ extern "C" const uint32_t *dd_joiner_build_idx(const dd_joiner *j) { return j->b
 extern "C" const uint32_t *dd_joiner_probe_idx(const dd_joiner *j) { return j->probe_idx; }
 
 extern "C" const void *dd_joiner_col_data(const dd_joiner *j, int32_t i) {
-    return j && i >= 0 && (size_t)i < j->col_data.size() ? j->col_data[(size_t)i] : nullptr;
+    return j ? j->cols.data_at(i) : nullptr;
 }
 
 extern "C" const uint8_t *dd_joiner_col_validity(const dd_joiner *j, int32_t i) {
-    return j && i >= 0 && (size_t)i < j->col_validity.size() ? j->col_validity[(size_t)i]
-                                                             : nullptr;
+    return j ? j->cols.validity_at(i) : nullptr;
 }
 
 extern "C" dd_status dd_joiner_kernel_ms(const dd_joiner *j, float *out5) {
@@ -3422,15 +3262,10 @@ struct dd_sorter {
     int64_t n_rows = 0;               /* output rows, after fetch */
     std::vector<int64_t> seg_offsets; /* [n_parts + 1] */
     uint32_t *perm = nullptr;         /* source row of each output row */
-    std::vector<void *> col_data;     /* per projected column; null only at zero rows */
-    std::vector<uint8_t *> col_validity; /* null when the source has none */
+    dd_out_cols cols;                 /* the projected columns */
     int32_t info[4] = {0, 0, DD_S_TILE, 0}; /* passes planned, passes run, tile rows, words */
     float kernel_ms[4] = {0, 0, 0, 0};      /* encode + census, passes, seg out, gather */
-    ~dd_sorter() {
-        (void)hipFree(perm);
-        for (void *p : col_data) (void)hipFree(p);
-        for (uint8_t *p : col_validity) (void)hipFree(p);
-    }
+    ~dd_sorter() { (void)hipFree(perm); }
 };
 
 extern "C" dd_status dd_sort_run(const dd_batch_desc *batch, const int32_t *key_cols,
@@ -3474,46 +3309,18 @@ extern "C" dd_status dd_sort_run(const dd_batch_desc *batch, const int32_t *key_
             return set_err(DD_ERR_INVALID, "sort: unknown key dtype");
         }
     }
-    if (n_proj < 0 || n_proj > DD_MAX_COLS || (n_proj > 0 && !proj_cols))
-        return set_err(DD_ERR_INVALID, "sort: projection list out of range");
-    for (int i = 0; i < n_proj; i++) {
-        if (proj_cols[i] < 0 || proj_cols[i] >= batch->n_cols)
-            return set_err(DD_ERR_INVALID, "sort: projected column index out of range");
-        const dd_col_desc &cd = batch->cols[proj_cols[i]];
-        if (cd.dtype == DD_DT_UTF8)
-            return set_err(DD_ERR_UNSUPPORTED, "sort: projection: a var-width (utf8 / "
-                                               "utf8view) column is not supported");
-        if (cd.dtype == DD_DT_DICT32)
-            return set_err(DD_ERR_UNSUPPORTED,
-                           "sort: projection: a dict32 column is not supported");
-        if (fixed_elem_size(cd.dtype) == 0)
-            return set_err(DD_ERR_INVALID, "sort: projection: unknown dtype");
-        if (cd.dtype == DD_DT_DEC128 && (uintptr_t)cd.data % 16)
-            return set_err(DD_ERR_INVALID, "sort: dec128 column data must be 16-byte aligned");
-    }
-    /* the layout, by dd_final_merge_run's checks */
-    if (n_segs < 1 || n_parts < 1)
-        return set_err(DD_ERR_INVALID, "sort: malformed segment layout: at least one segment "
-                                       "and one partition");
-    if (seg_offsets[0] != 0 || seg_offsets[n_segs] != n)
-        return set_err(DD_ERR_INVALID, "sort: malformed segment layout: seg_offsets must run "
-                                       "from 0 to n_rows");
-    std::vector<int64_t> in_off((size_t)n_parts + 1, 0), out_off((size_t)n_parts + 1, 0);
-    for (int s = 0; s < n_segs; s++) {
-        if (seg_offsets[s + 1] < seg_offsets[s])
-            return set_err(DD_ERR_INVALID, "sort: malformed segment layout: seg_offsets "
-                                           "decrease");
-        if (seg_part[s] < 0 || seg_part[s] >= n_parts)
-            return set_err(DD_ERR_INVALID, "sort: malformed segment layout: seg_part outside "
-                                           "[0, n_parts)");
-        in_off[(size_t)seg_part[s] + 1] += seg_offsets[s + 1] - seg_offsets[s];
-    }
+    if (dd_status st = dd_check_projection("sort: ", batch, proj_cols, n_proj)) return st;
+    std::vector<int64_t> rows_p;
+    if (dd_status st = dd_check_layout("sort: malformed segment layout: ", n, seg_offsets,
+                                       seg_part, n_segs, n_parts, &rows_p))
+        return st;
     /* rows per partition -> where each partition starts in the sorted order, and in the
      * output once fetch has cut it */
+    std::vector<int64_t> in_off((size_t)n_parts + 1, 0), out_off((size_t)n_parts + 1, 0);
     for (int p = 0; p < n_parts; p++) {
-        const int64_t rows = in_off[(size_t)p + 1];
+        const int64_t rows = rows_p[p];
         out_off[(size_t)p + 1] = out_off[p] + (fetch >= 0 && fetch < rows ? fetch : rows);
-        in_off[(size_t)p + 1] += in_off[p];
+        in_off[(size_t)p + 1] = in_off[p] + rows;
     }
     const int64_t n_out = out_off[n_parts];
 
@@ -3543,8 +3350,6 @@ extern "C" dd_status dd_sort_run(const dd_batch_desc *batch, const int32_t *key_
     auto so = std::unique_ptr<dd_sorter>(new dd_sorter());
     so->n_rows = n_out;
     so->seg_offsets = out_off;
-    so->col_data.assign((size_t)n_proj, nullptr);
-    so->col_validity.assign((size_t)n_proj, nullptr);
     so->info[3] = sk.n_words;
     if (n_out == 0) { /* no rows, or fetch = 0: empty segments, no device work */
         *out = so.release();
@@ -3562,39 +3367,25 @@ extern "C" dd_status dd_sort_run(const dd_batch_desc *batch, const int32_t *key_
     int32_t *d_seg_part = nullptr;
     uint64_t *words = nullptr, *wbuf[2] = {nullptr, nullptr};
     uint32_t *pbuf[2] = {nullptr, nullptr}, *census = nullptr, *hist = nullptr, *sums = nullptr;
-    if (!ws.alloc(&d_seg_off, ((size_t)n_segs + 1) * 8) ||
-        !ws.alloc(&d_seg_part, (size_t)n_segs * 4) ||
-        !ws.alloc(&d_in_off, ((size_t)n_parts + 1) * 8) ||
-        !ws.alloc(&d_out_off, ((size_t)n_parts + 1) * 8) ||
-        !ws.alloc(&words, (size_t)sk.n_words * (size_t)n * 8) ||
+    if (!ws.alloc(&words, (size_t)sk.n_words * (size_t)n * 8) ||
         !ws.alloc(&wbuf[0], (size_t)n * 8) || !ws.alloc(&wbuf[1], (size_t)n * 8) ||
         !ws.alloc(&pbuf[0], (size_t)n * 4) || !ws.alloc(&pbuf[1], (size_t)n * 4) ||
         !ws.alloc(&census, census_n * 4) || !ws.alloc(&hist, n_h * 4) ||
         !ws.alloc(&sums, (nb + 1) * 4))
         return set_err(DD_ERR_HIP, "sort: workspace alloc");
-    hipEvent_t ev[6] = {};
-    struct ev_guard {
-        hipEvent_t *e;
-        ~ev_guard() {
-            for (int i = 0; i < 6; i++)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } evg{ev};
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMemcpyAsync(d_seg_off, seg_offsets, ((size_t)n_segs + 1) * 8,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_seg_part, seg_part, (size_t)n_segs * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_in_off, in_off.data(), ((size_t)n_parts + 1) * 8,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_out_off, out_off.data(), ((size_t)n_parts + 1) * 8,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s)); /* pageable host sources: the copies have left them */
+    dd_events<6> ev;
+    HIP_TRY(ev.init());
+    HIP_TRY(ws.upload(&d_seg_off, seg_offsets, (size_t)n_segs + 1, s));
+    HIP_TRY(ws.upload(&d_seg_part, seg_part, (size_t)n_segs, s));
+    HIP_TRY(ws.upload(&d_in_off, in_off.data(), (size_t)n_parts + 1, s));
+    HIP_TRY(ws.upload(&d_out_off, out_off.data(), (size_t)n_parts + 1, s));
+    HIP_TRY(hipStreamSynchronize(s)); /* the uploads have left their pageable sources */
 
-    HIP_TRY(hipEventRecord(ev[0], s));
+    HIP_TRY(ev.record(0, s));
     HIP_TRY(hipMemsetAsync(census, 0, census_n * 4, s));
     HIP_TRY(dd_launch_sort_encode(&sk, n, d_seg_off, d_seg_part, n_segs, words, pbuf[0], census,
                                   s));
-    HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(ev.record(1, s));
     /* the run's one mid-run synchronisation: the census decides which passes run */
     std::vector<uint32_t> census_h(census_n);
     HIP_TRY(hipMemcpyAsync(census_h.data(), census, census_n * 4, hipMemcpyDeviceToHost, s));
@@ -3634,7 +3425,7 @@ extern "C" dd_status dd_sort_run(const dd_batch_desc *batch, const int32_t *key_
     so->info[0] = planned;
     so->info[1] = (int32_t)passes.size();
 
-    HIP_TRY(hipEventRecord(ev[2], s));
+    HIP_TRY(ev.record(2, s));
     int wi = -1, pi = 0, cur_word = -1; /* wbuf / pbuf holding the current word and perm */
     for (const dd_sort_pass &ps : passes) {
         const uint64_t *src = words + (size_t)ps.word * (size_t)n;
@@ -3655,32 +3446,21 @@ extern "C" dd_status dd_sort_run(const dd_batch_desc *batch, const int32_t *key_
         wi = wo;
         pi = 1 - pi;
     }
-    HIP_TRY(hipEventRecord(ev[3], s));
+    HIP_TRY(ev.record(3, s));
     HIP_TRY(hipMalloc((void **)&so->perm, (size_t)n_out * 4));
     HIP_TRY(dd_launch_sort_seg_out(pbuf[pi], d_in_off, d_out_off, n_parts, n_out, so->perm, s));
-    HIP_TRY(hipEventRecord(ev[4], s));
+    HIP_TRY(ev.record(4, s));
     dd_join_gather g;
     memset(&g, 0, sizeof(g));
-    for (int i = 0; i < n_proj; i++) {
-        const dd_col_desc &cd = batch->cols[proj_cols[i]];
-        const int c = g.n_cols++;
-        g.elem[c] = fixed_elem_size(cd.dtype);
-        g.src[c] = cd.data;
-        g.src_valid[c] = (const uint8_t *)cd.validity;
-        HIP_TRY(hipMalloc(&so->col_data[i], (size_t)n_out * g.elem[c]));
-        g.dst[c] = so->col_data[i];
-        if (cd.validity) {
-            HIP_TRY(hipMalloc((void **)&so->col_validity[i], (size_t)n_out));
-            g.dst_valid[c] = so->col_validity[i];
-        }
-    }
+    for (int i = 0; i < n_proj; i++)
+        HIP_TRY(so->cols.add(batch->cols[proj_cols[i]], n_out, false, &g));
     HIP_TRY(dd_launch_join_gather(&g, so->perm, n_out, s));
-    HIP_TRY(hipEventRecord(ev[5], s));
+    HIP_TRY(ev.record(5, s));
     HIP_TRY(hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&so->kernel_ms[0], ev[0], ev[1]);
-    (void)hipEventElapsedTime(&so->kernel_ms[1], ev[2], ev[3]);
-    (void)hipEventElapsedTime(&so->kernel_ms[2], ev[3], ev[4]);
-    (void)hipEventElapsedTime(&so->kernel_ms[3], ev[4], ev[5]);
+    ev.elapsed(&so->kernel_ms[0], 0, 1);
+    ev.elapsed(&so->kernel_ms[1], 2, 3);
+    ev.elapsed(&so->kernel_ms[2], 3, 4);
+    ev.elapsed(&so->kernel_ms[3], 4, 5);
     *out = so.release();
     return DD_OK;
 }
@@ -3696,11 +3476,11 @@ extern "C" dd_status dd_sorter_seg_offsets(const dd_sorter *so, int64_t *host_ou
 extern "C" const uint32_t *dd_sorter_perm(const dd_sorter *so) { return so->perm; }
 
 extern "C" const void *dd_sorter_col_data(const dd_sorter *so, int32_t i) {
-    return i >= 0 && i < (int32_t)so->col_data.size() ? so->col_data[i] : nullptr;
+    return so ? so->cols.data_at(i) : nullptr;
 }
 
 extern "C" const uint8_t *dd_sorter_col_validity(const dd_sorter *so, int32_t i) {
-    return i >= 0 && i < (int32_t)so->col_validity.size() ? so->col_validity[i] : nullptr;
+    return so ? so->cols.validity_at(i) : nullptr;
 }
 
 extern "C" dd_status dd_sorter_info(const dd_sorter *so, int32_t *out4) {
